@@ -16,7 +16,9 @@ independent maps, so a rank whose share is smaller than its GPU carries several 
 dependent map -- a muse! iteration -- has to do); --scaling weak gives every rank its own 512-sim block of a 512*N-sim map.
 Consecutive launches alternate over two lanes (streams with scratch and MAP slots of their own: MUSE_BENCH_LANES).
 
-Prints ONE JSON line on rank 0 (see the driver contract), with two extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times EXACTLY --steps steps (once;
+--min-seconds repeats the timed region), writes the last timed step's results with --dump-outputs DIR, and prints the line.
+Everything else is measured with --full only, which adds two objects:
   roofline      the solver kernel against the bound that actually binds it, per launch: "hbm" -- compulsory HBM bytes of the
                 placement the launch used / launch time against the 8 TB/s peak -- for the streaming placements; "valu" --
                 ALGORITHMIC work (operation counts per element from the source x the measured issue cost of each kind) /
@@ -28,7 +30,7 @@ Prints ONE JSON line on rank 0 (see the driver contract), with two extra objects
                 `algorithmic_bytes_d3` and is not a roofline.
   cpu_baseline  the CPU oracle (oracle/, a restatement of the reference: "port") timed on this box's
                 host cores on a bounded sample of the same workload (rank 0, N=1 only)
-and, because the driver's record keeps only FLAT scalars of `config` / `roofline` / `cpu_baseline`:
+and (--full as well), because a record of the line keeps only FLAT scalars of `config` / `roofline` / `cpu_baseline`:
   config.*      N = 1: the other BASELINE workloads (`funnel4_ms`, `noise_1e6_ms`, `smooth_1e5_ms` and their `_frac`: the pipelined
                 step, two lanes -- one for the stencil model), the muse! iteration (`muse_iter_us`, `muse_iter_steady_us`,
                 `muse_iter_line_search_us`), the 8-GPU share and the projections (`share_iter_us`, `proj_muse`, `proj_cfg4`, `proj_cfg5`),
@@ -939,6 +941,15 @@ def user_model_rates(M, device, N=10000, nsims=512):
     return out
 
 
+def dump_outputs(path, values_name, values, info):
+    """--dump-outputs: the last timed step's results as <path>/<name>.npy, float64 -- the per-problem values (scores, or the
+    finite-difference Jacobian columns) and every field of the solver's info records (iterations, f_calls, status, ...)."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, values_name + ".npy"), np.ascontiguousarray(values, dtype=np.float64))
+    for field in info.dtype.names:
+        np.save(os.path.join(path, field + ".npy"), np.ascontiguousarray(info[field], dtype=np.float64))
+
+
 def main_fd(args, M, torch, dist, world, rank, local_rank, sharded, tdev):
     """--workload cfg4_fd_H: BASELINE.json configs[3], get_H! by finite differences (src/muse.jl:407-446), 512 sims x 4 theta.  A step
     is ONE call: the rank's block of the flattened (sim, column) list (muse_fd_jacobian_columns) and, with N > 1, the exchange of
@@ -986,31 +997,35 @@ def main_fd(args, M, torch, dist, world, rank, local_rank, sharded, tdev):
         if not more:
             break
     dt = sum(rounds) / len(rounds)
-    # roofline leg: HIP events around every solver launch of a few calls; a call is two launches -- the fiducial MAP with the
-    # normals-only elements that fill the cache, then the perturbed problems (the dominant one)
-    ncalls = 16
-    prob.profile_begin(2 * ncalls + 8)
-    for _ in range(ncalls):
-        fd_call(M, prob, seed, lo, hi, sharded)
-    barrier()
-    kernel_ms = prob.profile_end()
-    fid_ms, fd_ms = kernel_ms[0::2], kernel_ms[1::2]
     assert np.all(info["status"] == 0), "a MAP solve did not converge in the timed region"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, "jacobian_columns", cols, info)
     nprob_job = 2 * nunits + 1                      # what the job needs; every rank repeats the one shared fiducial MAP
     nprob_rank = 2 * (hi - lo)
-    # compulsory HBM bytes of the perturbed launch (resident placement): a problem reads its simulation's cached normals n1, n2 and
-    # the fiducial MAP it starts from; its MAP is not stored (only the score leaves): 3 words per element
-    comp = 3 * 8 * N * nprob_rank
-    launch_s = float(fd_ms.mean()) * 1e-3
-    pinfo = prob.placement_info()
-    roof = {"bound": "hbm", "achieved": comp / launch_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": comp / launch_s / 1e9 / HBM_PEAK_GBS,
-            "traffic": None, "kernel": "map_score_kernel (BATCH_FD)", "placement": "resident" if pinfo["resident"] else "streaming",
-            "compulsory_bytes_per_launch": comp, "kernel_ms_mean": float(fd_ms.mean()), "fiducial_launch_ms_mean": float(fid_ms.mean()),
-            "launches_timed": int(fd_ms.size),
-            "note": "the perturbed problems' launch: per problem the simulation's cached normals (2 words per element) and the fiducial MAP "
-                    "(1) are read, one L-BFGS iteration runs on chip, nothing but the score is written; a mixed bound -- 3 words per "
-                    "element against ~60 fp64 operations",
-            "per_sim": {"f_calls_mean": float(info["f_calls"].mean()), "iterations_mean": float(info["iterations"].mean())}}
+    roof = None
+    if args.full:
+        # roofline leg: HIP events around every solver launch of a few calls; a call is two launches -- the fiducial MAP with the
+        # normals-only elements that fill the cache, then the perturbed problems (the dominant one)
+        ncalls = 16
+        prob.profile_begin(2 * ncalls + 8)
+        for _ in range(ncalls):
+            fd_call(M, prob, seed, lo, hi, sharded)
+        barrier()
+        kernel_ms = prob.profile_end()
+        fid_ms, fd_ms = kernel_ms[0::2], kernel_ms[1::2]
+        # compulsory HBM bytes of the perturbed launch (resident placement): a problem reads its simulation's cached normals n1, n2 and
+        # the fiducial MAP it starts from; its MAP is not stored (only the score leaves): 3 words per element
+        comp = 3 * 8 * N * nprob_rank
+        launch_s = float(fd_ms.mean()) * 1e-3
+        pinfo = prob.placement_info()
+        roof = {"bound": "hbm", "achieved": comp / launch_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": comp / launch_s / 1e9 / HBM_PEAK_GBS,
+                "traffic": None, "kernel": "map_score_kernel (BATCH_FD)", "placement": "resident" if pinfo["resident"] else "streaming",
+                "compulsory_bytes_per_launch": comp, "kernel_ms_mean": float(fd_ms.mean()), "fiducial_launch_ms_mean": float(fid_ms.mean()),
+                "launches_timed": int(fd_ms.size),
+                "note": "the perturbed problems' launch: per problem the simulation's cached normals (2 words per element) and the fiducial MAP "
+                        "(1) are read, one L-BFGS iteration runs on chip, nothing but the score is written; a mixed bound -- 3 words per "
+                        "element against ~60 fp64 operations",
+                "per_sim": {"f_calls_mean": float(info["f_calls"].mean()), "iterations_mean": float(info["iterations"].mean())}}
     out = {
         "metric": "MC sims/sec (MAP+score)", "value": nprob_job * args.steps / dt, "unit": "sims/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
@@ -1021,9 +1036,11 @@ def main_fd(args, M, torch, dist, world, rank, local_rank, sharded, tdev):
                    "theta": w["theta"], "step": w["step"],
                    "parallelism": f"the flattened (sim, column) list in {world} contiguous block(s) (src/muse.jl:327-333 across ranks), one exchange "
                                   "of the column blocks per call" + (f" ({collective}, {seen} ranks seen)" if collective else "")},
-        "timed_rounds": len(rounds), "timed_seconds": sum(rounds), "roofline": roof,
+        "timed_rounds": len(rounds), "timed_seconds": sum(rounds),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if roof is not None:
+        out["roofline"] = roof
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(w["model"], N, w["theta"], seed, cpu_seconds=15.0)
         out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
     prob.close()
@@ -1044,14 +1061,22 @@ def parse_args(argv=None):
     ap.add_argument("--scaling", default=None, choices=["strong", "weak"],
                     help="with --gpus N > 1: strong (default) = the step's nsims shared by the ranks, weak = nsims per rank")
     ap.add_argument("--split", type=int, default=-1, help="workgroups per element (-1: by the rank's element count)")
-    ap.add_argument("--min-seconds", type=float, default=0.5,
+    ap.add_argument("--min-seconds", type=float, default=0.0,
                     help="repeat the timed region (EXACTLY --steps steps between barriers, every time) until this much "
-                         "time has been measured; ms_per_step is the mean over the repetitions")
+                         "time has been measured; ms_per_step is the mean over the repetitions (default 0: the timed region "
+                         "runs once, --steps steps in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the roofline leg (HIP events around every launch), the CPU baseline, "
+                         "the other workloads and projections (N = 1) and the sharded extras (N > 1); --no-cpu-baseline and "
+                         "--no-extra leave parts of it out.  Without it a run times the headline steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (scores and solver info of rank 0's "
+                         "block; with --gpus 1 the whole step) as DIR/<name>.npy, float64")
     ap.add_argument("--nsims", type=int, default=0, help="development aid: sims per step instead of the workload's own "
                     "(e.g. 64 = one rank's share of the strongly scaled 8-GPU step, on one GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the untimed muse!/get_H! rates (N = 1) / the sharded muse! loop, configs[3] "
-                    "and configs[4] beside the headline (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the untimed muse!/get_H! rates (N = 1) / the sharded muse! "
+                    "loop, configs[3] and configs[4] beside the headline (N > 1)")
     ap.add_argument("--small", action="store_true", help="development aid: the N > 1 extras at sizes that eight processes can share ONE GPU with")
     return ap.parse_args(argv)
 
@@ -1370,19 +1395,24 @@ def main():
                 break
         dt = sum(rounds) / len(rounds)
         host_us = {"enqueue": 1e6 * host_t[0] / args.steps, "wait_and_collect": 1e6 * host_t[1] / args.steps}
-        # roofline leg: the same steps again with a HIP event pair around every solver launch, recorded on the stream the
-        # kernel is launched on
-        nprof = min(max(args.steps, 64), 256)
-        prob.profile_begin(nprof + 8)
-        run_steps(nprof)
-        barrier()
-        kernel_ms = prob.profile_end()
-        try:
-            clock_hz = prob.profile_clock_hz()   # in-kernel: d(s_memtime) / d(s_memrealtime) x 100 MHz of a profiled launch
-        except M.MuseError:
-            clock_hz = None
+        # the last timed step, copied out of the result buffers (the roofline leg below reuses them): rank 0's block of it --
+        # a launch carrying several maps returns them map after map
         g, info = results[-1]
+        last = (np.array(g).reshape(-1, nlocal, nth)[-1], np.array(info).reshape(-1, nlocal)[-1]) if nlocal else None
         assert np.all(info["status"] == 0), "a MAP solve did not converge in the timed region"
+        kernel_ms = clock_hz = None
+        if args.full:
+            # roofline leg: the same steps again with a HIP event pair around every solver launch, recorded on the stream the
+            # kernel is launched on
+            nprof = min(max(args.steps, 64), 256)
+            prob.profile_begin(nprof + 8)
+            run_steps(nprof)
+            barrier()
+            kernel_ms = prob.profile_end()
+            try:
+                clock_hz = prob.profile_clock_hz()   # in-kernel: d(s_memtime) / d(s_memrealtime) x 100 MHz of a profiled launch
+            except M.MuseError:
+                clock_hz = None
         pinfo = prob.placement_info()
         if state["capi"]:
             prob.comm_destroy()
@@ -1390,7 +1420,7 @@ def main():
         return {"dt": dt, "rounds": rounds, "host_us": host_us, "kernel_ms": kernel_ms, "info": info, "split": split,
                 "maps_per_launch": state["nmaps"],
                 "collective": collective, "ranks_seen": seen, "pinfo": pinfo, "value": total_sims * args.steps / dt,
-                "clock_hz": clock_hz, "launches": -(-args.steps // state["nmaps"])}
+                "clock_hz": clock_hz, "launches": -(-args.steps // state["nmaps"]), "last": last}
 
     # The host loop must keep three launches ahead of a ~50 us kernel: a full collection of the interpreter's cyclic GC
     # (torch alone brings more than a million tracked objects; measured 40-60 ms, once, a few hundred steps into a run)
@@ -1407,11 +1437,6 @@ def main():
         best = ran[best_t]
         dt, rounds, host_us, kernel_ms, info, split, collective, pinfo = (best[k] for k in (
             "dt", "rounds", "host_us", "kernel_ms", "info", "split", "collective", "pinfo"))
-
-        prow_ok = world == 1 and split == 1 and not sharded
-        launch_s = dt / best["launches"] if world == 1 else float(kernel_ms.mean()) * 1e-3
-        primary = roofline_object(args.workload, model, N, info, pinfo, kernel_ms, launch_s, best["clock_hz"], lanes,
-                                  1e3 * dt / best["launches"], prow_ok)
 
         out = {
             "metric": "MC sims/sec (MAP+score)",
@@ -1440,9 +1465,13 @@ def main():
                                         "2-3x, bounded by one problem's latency plus the exchange")},
             "timed_rounds": len(rounds), "timed_seconds": sum(rounds),
             "ms_per_step_min_round": 1e3 * min(rounds) / args.steps, "ms_per_step_max_round": 1e3 * max(rounds) / args.steps,
-            "roofline": primary,
             "host_us_per_step": host_us,
         }
+        if kernel_ms is not None:   # (--full: the roofline leg ran)
+            prow_ok = world == 1 and split == 1 and not sharded
+            launch_s = dt / best["launches"] if world == 1 else float(kernel_ms.mean()) * 1e-3
+            out["roofline"] = roofline_object(args.workload, model, N, info, pinfo, kernel_ms, launch_s, best["clock_hz"], lanes,
+                                              1e3 * dt / best["launches"], prow_ok)
         if sharded:
             # both exchanges of the same run, side by side: did RCCL see N ranks, and what did each cost
             out["transport"] = best_t
@@ -1451,8 +1480,8 @@ def main():
                     {"value": m["value"], "ms_per_step": 1e3 * m["dt"] / args.steps, "collective": m["collective"],
                      "ranks_seen": m["ranks_seen"], "element_split": m["split"],
                      "pipelining": f"maps_per_launch={m['maps_per_launch']}",
-                     "kernel_ms_mean": float(m["kernel_ms"].mean()), "host_us_per_step": m["host_us"],
-                     "timed_rounds": len(m["rounds"])})
+                     "host_us_per_step": m["host_us"], "timed_rounds": len(m["rounds"]),
+                     **({} if m["kernel_ms"] is None else {"kernel_ms_mean": float(m["kernel_ms"].mean())})})
                 for t, m in measured.items()}
         return out
 
@@ -1484,7 +1513,11 @@ def main():
             timer.cancel()
     out = build_line(measured)
     best_t = out.get("transport")
-    if rank == 0 and world == 1 and not sharded and not args.no_extra:
+    if args.dump_outputs and rank == 0:
+        last = measured[best_t]["last"]   # (one GPU: the only "transport", None)
+        if last is not None:
+            dump_outputs(args.dump_outputs, "scores", *last)
+    if args.full and rank == 0 and world == 1 and not sharded and not args.no_extra:
         out["extra"] = extra_rates(M, prob, model, N, nth, theta, nsims, seed, local_rank)
         if args.workload == "funnel_1e4":
             # the other BASELINE workloads, briefly, so that they are in the driver's line too (each <= ~0.3 s of timed steps)
@@ -1501,10 +1534,10 @@ def main():
             except Exception as e:  # an extra: never at the cost of the line
                 out["extra"]["user_model"] = {"skipped": f"{type(e).__name__}: {e}"}
         flat_single(out)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(model, N, theta, seed)
         out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
-    if sharded and not args.no_extra and args.workload == "funnel_1e4":
+    if args.full and sharded and not args.no_extra and args.workload == "funnel_1e4":
         # beside the headline's independent maps: the dependent path and the two workloads BASELINE.json puts on 8 GPUs, over THESE ranks
         prob.close()
         # (a collective of the extras that never completes -- a peer that died, a board wait -- must not cost the line: the same

@@ -102,3 +102,26 @@ def test_flat_scalars_of_the_single_gpu_extras_survive_missing_parts():
     bench.flat_single(out)
     assert out["config"]["funnel4_ms"] == 0.058 and "noise_1e6_ms" not in out["config"] and "proj_cfg4" not in out["config"]
     bench.flat_single({"config": {}})    # (--no-extra: nothing to flatten)
+
+
+def test_plain_arguments_time_exactly_the_steps_and_full_is_opt_in():
+    """A plain run's timed region is --steps steps, once; the roofline leg, the extras and the CPU baseline need --full."""
+    bench = load_bench()
+    a = bench.parse_args(["--gpus", "1", "--steps", "9", "--warmup", "3"])
+    assert a.steps == 9 and a.warmup == 3 and a.min_seconds == 0 and a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_every_array_as_float64(tmp_path):
+    import numpy as np
+    bench = load_bench()
+    info = np.zeros(3, dtype=[("iterations", "<i4"), ("f_calls", "<i4"), ("status", "<i4"), ("f_min", "<f8")])
+    info["f_calls"] = [3, 4, 5]
+    info["f_min"] = [0.5, 1.5, 2.5]
+    g = np.arange(6, dtype=np.float64).reshape(3, 2)
+    bench.dump_outputs(str(tmp_path / "d"), "scores", g, info)
+    assert sorted(os.listdir(tmp_path / "d")) == ["f_calls.npy", "f_min.npy", "iterations.npy", "scores.npy", "status.npy"]
+    for name, want in (("scores", g), ("f_calls", [3, 4, 5]), ("f_min", [0.5, 1.5, 2.5])):
+        got = np.load(tmp_path / "d" / f"{name}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, want)

@@ -6,11 +6,13 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BENCH = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "4", "--min-seconds", "0",
+# (--full: these tests read the roofline object and the extras, which a plain run leaves out)
+BENCH = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "4", "--min-seconds", "0", "--full",
          "--no-cpu-baseline", "--no-extra"]
 
 
@@ -105,7 +107,7 @@ def test_bench_under_torch_distributed_run(gpu):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         e.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2", "--min-seconds", "0", "--small"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2", "--min-seconds", "0", "--full", "--small"]
     p = subprocess.run(cmd, env=e, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -171,13 +173,14 @@ def test_bench_single_gpu_runs_of_the_8_gpu_workloads(gpu):
 
 
 def test_bench_default_line_carries_the_other_workloads_and_projections(gpu):
-    """The driver's command as it is run (`python bench.py`: extras on; only the CPU baseline left out here): the other BASELINE
+    """The full run (`python bench.py --full`: extras on; only the CPU baseline left out here): the other BASELINE
     workloads are timed inside it, the two 8-GPU workloads are projected, and the dependent path's 8-GPU share -- the sharded loop as
     ONE persistent launch through a one-rank communicator -- is in the line with both kinds of iteration told apart."""
     e = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         e.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--min-seconds", "0", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--min-seconds", "0", "--full",
+                        "--no-cpu-baseline"],
                        env=e, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-4000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -204,3 +207,30 @@ def test_bench_default_line_carries_the_other_workloads_and_projections(gpu):
     assert 0 < r["hbm_frac"] < 1 and 0 < r["frac_kernel_time"] <= 1 and r["frac_definition"].startswith("pipelined")
     assert set(sh["projected_by_regime"]) <= {"line_search", "converged_at_start"} and sh["projected_by_regime"]
     assert "line_search" in x["muse_run"]["by_regime"]
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(gpu, O, tmp_path):
+    """`python bench.py --steps K --warmup W` without --full: EXACTLY K timed steps, the headline fields and nothing that takes a run
+    of its own (no roofline leg, no extras, no CPU baseline); --dump-outputs writes the last timed step's scores and solver infos,
+    which are the oracle's for the same 512 simulations (the same parity as tests/test_gpu_parity.py)."""
+    e = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        e.pop(k, None)
+    out = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                        "--dump-outputs", str(out)], env=e, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-4000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["timed_rounds"] == 1 and d["unit"] == "sims/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["value"] > 0 and abs(d["value"] - 512 / (1e-3 * d["ms_per_step"])) < 1e-6 * d["value"]
+    assert abs(d["timed_seconds"] - 7e-3 * d["ms_per_step"]) < 1e-9
+    assert not {"roofline", "extra", "cpu_baseline"} & set(d), sorted(d)
+    g = np.load(out / "scores.npy")
+    assert g.dtype == np.float64 and g.shape == (512, 1)
+    go, _, io = O.map_and_score_batch("funnel", 10000, 0, 0, 512, [1.0], atol=1e-2, z0_mode=0, nthreads=8)
+    for field in ("iterations", "f_calls", "status"):
+        got = np.load(out / f"{field}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, io[field].astype(np.float64)), field
+    np.testing.assert_allclose(g, go, rtol=1e-10)

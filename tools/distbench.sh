@@ -7,7 +7,7 @@ d = json.loads(open('/tmp/b.json').read())
 print(sys.argv[1], round(d["value"]), round(1e3 * d["ms_per_step"], 1), "us/step; kernel", round(1e3 * d["roofline"]["kernel_ms_mean"], 1), "us; host", d["host_us_per_step"])
 PY
 }
-B="python bench.py --steps 300 --warmup 30 --no-cpu-baseline"
+B="python bench.py --steps 300 --warmup 30 --min-seconds 0.5 --full --no-cpu-baseline"
 $B 2>&1 | grep "^{" | tail -1 > /tmp/b.json; show plain
 MUSE_BENCH_FORCE_DIST=1 $B 2>&1 | grep "^{" | tail -1 > /tmp/b.json; show rccl
 MUSE_BENCH_FORCE_DIST=1 MUSE_COMM_ONE_STREAM=1 $B 2>&1 | grep "^{" | tail -1 > /tmp/b.json; show rccl-one-stream

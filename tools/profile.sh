@@ -15,5 +15,5 @@ for W in "$@"; do
   rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_$W -- python3 $R/bench.py --steps 10 --warmup 2 --min-seconds 0 --no-cpu-baseline --no-extra --workload $W > $OUT/bench_write_$W.log 2>&1
   rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_WAVES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_LDS --output-format csv -d $OUT/pmc_sq_$W -- python3 $R/bench.py --steps 10 --warmup 2 --min-seconds 0 --no-cpu-baseline --no-extra --workload $W > $OUT/bench_sq_$W.log 2>&1
 done
-python3 $R/bench.py --steps 300 --warmup 30 > $OUT/bench_full.json 2> $OUT/bench_full.err
+python3 $R/bench.py --steps 300 --warmup 30 --min-seconds 0.5 --full > $OUT/bench_full.json 2> $OUT/bench_full.err
 tail -1 $OUT/bench_full.json | cut -c1-200
