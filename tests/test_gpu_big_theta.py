@@ -11,7 +11,7 @@ import os
 import numpy as np
 import pytest
 
-from test_gpu_parity import assert_same_path_or_close
+from test_gpu_parity import assert_same_path_or_close, hess_inf_cubic
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -87,7 +87,8 @@ def test_big_theta_user_model(gpu, M, O):
         g, info = prob.map_and_score_batch(4, 0, 4, theta, atol=1e-6, z0_mode=0)
         go, zho, io = O.map_and_score_batch("user", N, 4, 0, 4, theta, atol=1e-6, z0_mode=0)
         zh = prob.get_zhat(0, 4)
-        assert_same_path_or_close(info, io, zh, zho, g, go, 1e-6, theta, "user", ctx="cubic, 11 components", z_atol=1e-8, g_rtol=1e-9)
+        assert_same_path_or_close(info, io, zh, zho, g, go, 1e-6, theta, "user", ctx="cubic, 11 components", z_atol=1e-8, g_rtol=1e-9,
+                                  hess_inf=hess_inf_cubic(theta, zho, 1e-6))
         Hi, its = prob.implicit_H_batch(5, 0, 2, theta)
         for s in range(2):
             Ho, io = O.implicit_H("user", N, 5, s, theta, atol=1e-1, cg_maxiter=100)

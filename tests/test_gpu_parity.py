@@ -16,14 +16,40 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def assert_same_path_or_close(info, io, z, zo, g, go, atol, theta, model, ctx="", z_atol=1e-9, g_rtol=1e-10):
+def hess_inf_cubic(theta, zo, atol):
+    """The infinity norm of grad_z^2 f of the cubic model (models/cubic.h) near its MAP: iv + h'^2 - (x - h) h'', h' = 1 + 0.3 z^2,
+    h'' = 0.6 z.  At a MAP (x - h) h' = iv z +- atol, so |(x - h) h''| <= iv 0.6 z^2 / h' + 0.6 |z| atol <= 2 iv + 0.6 |z| atol."""
+    iv, m = float(np.exp(-np.min(theta))), float(np.abs(zo).max())
+    return 3.0 * iv + (1.0 + 0.3 * m * m) ** 2 + 0.6 * m * atol
+
+
+def hess_inf_pair(theta):
+    """... of the two-parameter family of normal_mean_var.h: 1 + e^{-tau_k}, tau = the second half of theta."""
+    theta = np.asarray(theta, dtype=np.float64)
+    return 1.0 + float(np.exp(-np.min(theta[theta.size // 2:])))
+
+
+def assert_same_path_or_close(info, io, z, zo, g, go, atol, theta, model, ctx="", z_atol=1e-9, g_rtol=1e-10, hess_inf=None):
     """info/io: solver infos (GPU / oracle) of the same elements; z, zo: MAPs [n, N]; g, go: scores [n, ntheta] or None.
-    z_atol / g_rtol: the tolerances on the same path (the defaults are the stated ones for the built-in, quadratic models)."""
+    z_atol / g_rtol: the tolerances on the same path (the defaults are the stated ones for the built-in, quadratic models).
+    On the same path the records must agree too: f_min to rtol 1e-11 (test_zhat_at_theta's), and gnorm to L z_atol plus the
+    rounding of two fp64 gradients, L = hess_inf, the infinity norm of grad_z^2 f.  For the built-in models L = 1 + e^{-theta_min}
+    (the stencil's A^T A has row sums 1); a caller that names "funnel" for a header model passes its own L (hess_inf_cubic,
+    hess_inf_pair, ...), and one that names no model it can bound ("user") gets no gnorm comparison."""
     info, io = np.atleast_1d(info), np.atleast_1d(io)
     z, zo = np.atleast_2d(z), np.atleast_2d(zo)
     assert np.array_equal(info["status"], io["status"]), ctx
     same = (info["iterations"] == io["iterations"]) & (info["f_calls"] == io["f_calls"])
     np.testing.assert_allclose(z[same], zo[same], rtol=0, atol=z_atol, err_msg=ctx)
+    np.testing.assert_allclose(info["f_min"][same], io["f_min"][same], rtol=1e-11, err_msg=ctx)
+    if hess_inf is None and model in ("funnel", "noise", "smooth"):
+        hess_inf = 1.0 + float(np.exp(-np.min(theta)))
+    if hess_inf is not None and same.any():
+        # |grad_i| evaluated on absolute values is at most L (1 + |z|)^3 near a MAP of these models (|x| <= |h(z)| + |r|, h at most
+        # cubic); each side's fp64 gradient is within 8 u of that
+        m = float(np.abs(zo[same]).max())
+        gscale = 16 * 2.0**-53 * hess_inf * (1.0 + m) ** 3
+        assert np.all(np.abs(info["gnorm"][same] - io["gnorm"][same]) <= hess_inf * z_atol + gscale), (ctx, "gnorm")
     if g is not None:
         np.testing.assert_allclose(np.atleast_2d(g)[same], np.atleast_2d(go)[same], rtol=g_rtol, err_msg=ctx)
     if not same.all():  # (never taken by a committed case: see the module docstring)

@@ -161,7 +161,7 @@ def make(M, x, N, nth, placement, split, prior=None):
 @pytest.mark.gpu
 @pytest.mark.parametrize("N,nth,theta,placement,split", PLACEMENTS)
 def test_pair_model_hip_against_the_checker(gpu, M, O, N, nth, theta, placement, split):
-    from test_gpu_parity import assert_same_path_or_close
+    from test_gpu_parity import assert_same_path_or_close, hess_inf_pair
     theta = np.asarray(theta)
     with O.user_model(HEADER, NAME):
         truth = np.concatenate([np.full(nth // 2, 0.3), np.zeros(nth // 2)])
@@ -185,7 +185,8 @@ def test_pair_model_hip_against_the_checker(gpu, M, O, N, nth, theta, placement,
             g, info = prob.map_and_score_batch(42, 3, 3 + nsims, theta, include_data=True, atol=1e-6, z0_mode=z0_mode)
             go, zo, io = O.map_and_score_batch("user", N, 42, 3, 3 + nsims, theta, atol=1e-6, x_data=xdata, z0_mode=z0_mode)
             zh = prob.get_zhat(0, nsims + 1)
-            same = assert_same_path_or_close(info, io, zh, zo, g, go, 1e-6, theta, "funnel", ctx=f"z0_mode {z0_mode}", g_rtol=1e-10)
+            same = assert_same_path_or_close(info, io, zh, zo, g, go, 1e-6, theta, "funnel", ctx=f"z0_mode {z0_mode}", g_rtol=1e-10,
+                                             hess_inf=hess_inf_pair(theta))
             assert same.all(), (info["iterations"], io["iterations"], info["f_calls"], io["f_calls"])
             assert np.all(info["status"] == 0)
         # ... and the MAP in closed form: zhat = (x + iv mu) / (1 + iv)
