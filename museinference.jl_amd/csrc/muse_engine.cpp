@@ -44,8 +44,8 @@ static int fail(int code, const std::string& msg) {
             return fail(MUSE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                  \
     } while (0)
 
-// What a solver launch owns exclusively while it runs.  A context has one set of these per LANE; the lane a call uses is
-// swapped into the context's own fields of the same names (use_lane), so that the launch code below is written once.
+// What a solver launch owns exclusively while it runs.  A context has one set of these per LANE, and they live nowhere
+// else; ctx->lane points at the lane the current call works on (lane 0 unless map_async_impl selects the area's: use_lane).
 // One lane (the default): launches of a context run one after the other on its stream.  muse_set_concurrency(ctx, n):
 // result area r runs on lane r mod n -- a stream, a workgroup scratch, a ticket counter and a cluster state of its own --
 // so that a launch can start on the compute units the previous one has already left, instead of behind its last workgroup
@@ -56,30 +56,26 @@ struct LaneState {
     double* scratch = nullptr;
     size_t scratch_doubles = 0;
     int* counter = nullptr;
-    unsigned int ticket_base = 0;
-    double* cl_part = nullptr;
-    unsigned int* cl_state = nullptr;
+    unsigned int ticket_base = 0;  // value of the device ticket counter when the next launch starts
+    double* cl_part = nullptr;           // [cl_cap][kClusterSlotDoubles]
+    unsigned int* cl_state = nullptr;    // [cl_cap] granule-exchange epochs
     int cl_cap = 0;
-    int* error_flag = nullptr;
+    int* error_flag = nullptr;           // pinned, device-mapped: [0] the error word, [1] the cluster epoch
     double* zhat = nullptr;        // the lane's resident MAP slots: a streaming solve works IN its slot, so maps in flight at once
     int64_t zhat_slots = 0;        // cannot share them
-    bool ready = false;
+    bool ready = false;            // the lane's resources exist (create_lane)
 };
 
 struct muse_ctx {
-    LaneState lanes[kMaxLanes];   // lanes[cur_lane] is stale while that lane is swapped in
-    int nlanes = 1, cur_lane = 0;
+    LaneState lanes[kMaxLanes];   // lane 0 from muse_ctx_create on, the others from their first use
+    LaneState* lane = nullptr;    // the lane the current call works on: lanes[0] at every entry (check_ctx) and every return
+    int nlanes = 1;
     int model = 0, ntheta = 1, device = 0, placement = -1, num_cus = 0;
     int64_t N = 0, ld = 0;
     int64_t bnd[kBigTheta + 1] = {0};
-    hipStream_t stream = nullptr, own_stream = nullptr;
+    hipStream_t own_stream = nullptr;   // lane 0's stream until muse_set_stream replaces it
     double* x_data = nullptr;
     bool has_data = false;
-    double* zhat = nullptr;
-    int64_t zhat_slots = 0;
-    double* scratch = nullptr;
-    size_t scratch_doubles = 0;
-    int* counter = nullptr;
     double* tmp = nullptr;  // 3 vectors for the per-sim operator entry points
     SampleSd* tsample_dev = nullptr;   // sampling thetas of a finite-difference map (grown on demand)
     SampleSd* tsample_pin = nullptr;
@@ -114,19 +110,12 @@ struct muse_ctx {
     long consts_len[4] = {0, 0, 0, 0};
     bool has_consts = false;
     bool nc_auto = true;                 // muse_set_normals_cache: plain maps may store / load the normals of repeated simulations
-    double* cl_part = nullptr;           // [cl_cap][kClusterSlotDoubles]
-    unsigned int* cl_state = nullptr;    // [cl_cap] granule-exchange epochs
-    int cl_cap = 0;
-    int* error_flag = nullptr;           // pinned, device-mapped
     double* fid_norm = nullptr;          // [2][ld]: the standard normals of get_H!'s fiducial stream, drawn by a kernel of its own (fd_values_impl)
     unsigned int* fid_flag = nullptr;    // device word: the tag of the last fiducial MAP published inside a finite-difference launch
     unsigned int fid_tag = 0;            // (fd_values_impl; grows with every such launch)
     int debug = 0;                       // muse_debug_flags
     Switches sw;                         // the environment switches as muse_ctx_create found them (switches.hpp)
     int split = 0;                 // muse_set_element_split: 0 = by N alone, >= 2 = workgroups per element
-    unsigned int ticket_base = 0;  // value of the device ticket counter when the next launch starts
-    hipEvent_t launch_done = nullptr;  // set around launch_batch: the event this launch signals when it completes
-    bool launch_done_used = false;
     bool timing = false;           // record an event pair around every solver launch (muse_set_timing; costs ~12 us per launch)
     unsigned long long* stamps = nullptr;
     int64_t stamps_cap = 0;
@@ -257,39 +246,38 @@ static int64_t place_scratch_vectors(int pl) {
 }
 
 static int ensure_zhat(muse_ctx* c, int64_t slots) {
-    if (slots <= c->zhat_slots) return MUSE_OK;
+    if (slots <= c->lane->zhat_slots) return MUSE_OK;
     double* nz = nullptr;
     if (hipMalloc(&nz, (size_t)slots * c->ld * sizeof(double)) != hipSuccess)
         return fail(MUSE_ERR_ALLOC, "hipMalloc(zhat) failed");
-    HIPCHK(hipMemsetAsync(nz, 0, (size_t)slots * c->ld * sizeof(double), c->stream));
-    if (c->zhat) {
-        HIPCHK(hipMemcpyAsync(nz, c->zhat, (size_t)c->zhat_slots * c->ld * sizeof(double), hipMemcpyDeviceToDevice,
-                              c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipFree(c->zhat));
+    HIPCHK(hipMemsetAsync(nz, 0, (size_t)slots * c->ld * sizeof(double), c->lane->stream));
+    if (c->lane->zhat) {
+        HIPCHK(hipMemcpyAsync(nz, c->lane->zhat, (size_t)c->lane->zhat_slots * c->ld * sizeof(double), hipMemcpyDeviceToDevice,
+                              c->lane->stream));
+        HIPCHK(hipStreamSynchronize(c->lane->stream));
+        HIPCHK(hipFree(c->lane->zhat));
     }
-    c->zhat = nz;
-    c->zhat_slots = slots;
+    c->lane->zhat = nz;
+    c->lane->zhat_slots = slots;
     return MUSE_OK;
 }
 static int ensure_scratch(muse_ctx* c, size_t doubles) {
-    if (doubles <= c->scratch_doubles) return MUSE_OK;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->scratch) HIPCHK(hipFree(c->scratch));
-    c->scratch = nullptr;
-    c->scratch_doubles = 0;
-    if (hipMalloc(&c->scratch, doubles * sizeof(double)) != hipSuccess)
+    if (doubles <= c->lane->scratch_doubles) return MUSE_OK;
+    HIPCHK(hipStreamSynchronize(c->lane->stream));
+    if (c->lane->scratch) HIPCHK(hipFree(c->lane->scratch));
+    c->lane->scratch = nullptr;
+    c->lane->scratch_doubles = 0;
+    if (hipMalloc(&c->lane->scratch, doubles * sizeof(double)) != hipSuccess)
         return fail(MUSE_ERR_ALLOC, "hipMalloc(scratch) failed");
-    c->scratch_doubles = doubles;
+    c->lane->scratch_doubles = doubles;
     return MUSE_OK;
 }
 // The normals cache exists only where the sampler is a large share of a problem and the placement supports it
 // (the LDS-resident layout, 4096 < N <= kMaxResidentN); a failed allocation just means no caching.
-static bool ncache_applies(const muse_ctx* c);
 static bool ensure_ncache(muse_ctx* c, int64_t slots) {
     if (!ncache_applies(c)) return false;
     if (slots <= c->ncache_slots) return true;
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return false;
+    if (hipStreamSynchronize(c->lane->stream) != hipSuccess) return false;
     if (c->ncache) hipFree(c->ncache);
     c->ncache = nullptr;
     c->ncache_slots = 0;
@@ -318,7 +306,7 @@ static bool ncache_holds(const muse_ctx* c, uint64_t seed, int64_t sim0, int64_t
 }
 static int ensure_results(muse_ctx* c, int area, int64_t n) {
     if (n <= c->res_cap[area]) return MUSE_OK;
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipStreamSynchronize(c->lane->stream));
     if (c->scores_pin[area]) HIPCHK(hipHostFree(c->scores_pin[area]));
     const int64_t cap = n + n / 2 + 16;
     HIPCHK(hipHostMalloc(&c->scores_pin[area], result_bytes(c, cap), hipHostMallocDefault));
@@ -329,8 +317,9 @@ static int ensure_results(muse_ctx* c, int area, int64_t n) {
     return MUSE_OK;
 }
 
-// Fill the common fields and launch the solver for `a.nproblems` elements.
-static int launch_batch(muse_ctx* c, BatchArgs& a) {
+// What every launch of a solver or loop kernel takes from the context and from the launching lane, the same way (launch_batch,
+// run_loop_launch); `stamp_rows`: the rows a launch of this kind writes into the debug stamps.
+static void common_args(const muse_ctx* c, BatchArgs& a, int64_t stamp_rows) {
     a.N = c->N;
     a.ld = c->ld;
     a.ntheta = c->ntheta;
@@ -339,20 +328,35 @@ static int launch_batch(muse_ctx* c, BatchArgs& a) {
         a.bnd32[k] = k < nblocks_of(c->ntheta) ? (int)c->bnd[k] : 0x7fffffff;
     }
     a.x_data = c->x_data;
-    if (!a.zhat) a.zhat = c->zhat;
-    a.work_counter = c->counter;
+    if (!a.zhat) a.zhat = c->lane->zhat;
+    a.work_counter = c->lane->counter;
     if (a.nmaps <= 1) {
         a.nmaps = 1;
         a.n_per_map = a.nproblems;
         a.map_stride = a.nproblems;
     }
     a.debug = c->debug & 0xffff;   // (bits 16-21 are host-side: switches.hpp)
-    a.stamps = (c->stamps && a.nproblems <= c->stamps_cap) ? c->stamps : nullptr;
+    a.stamps = (c->stamps && stamp_rows <= c->stamps_cap) ? c->stamps : nullptr;
+    a.csize = 1;
+    a.error_flag = c->lane->error_flag;
+}
+// Attach a normals cache to a launch: `cache` holds (mode 2: the launch loads them) or takes (mode 1: it stores them) the standard
+// normals of simulations [sim0, sim0 + count).
+static void attach_ncache(BatchArgs& a, double* cache, int64_t sim0, int64_t count, int mode) {
+    a.ncache = cache;
+    a.ncache_sim0 = sim0;
+    a.ncache_count = (int)count;
+    a.ncache_mode = mode;
+}
+
+// Fill the common fields and launch the solver for `a.nproblems` elements.  `done`: an event the launch itself signals when it
+// completes (NULL: none) -- a launch that returns MUSE_OK carries it.
+static int launch_batch(muse_ctx* c, BatchArgs& a, hipEvent_t done = nullptr) {
+    common_args(c, a, a.nproblems);
     a.clock_out = c->prof_on ? c->clock_pin : nullptr;  // roofline leg only
     const bool implicit = a.kind == BATCH_IMPLICIT;
     const int pl = implicit ? (use_cluster(c) ? P_C256 : P_S512) : choose_place(c);
     int grid = c->num_cus * place_wgs_per_cu(pl);
-    a.csize = 1;
     // cluster placements need every member resident at once: a device-side collective of the previous step (RCCL transport:
     // its kernel holds compute units on a high-priority stream until the slowest peer arrives) keeps a share of the GPU
     if (place_is_cluster(pl) && c->comm_reserve_cus > 0 && c->num_cus > 2 * c->comm_reserve_cus)
@@ -375,22 +379,22 @@ static int launch_batch(muse_ctx* c, BatchArgs& a) {
         if (ncl < 1) ncl = 1;
         a.nclusters = ncl;
         grid = ncl * a.csize;
-        const bool wrap = c->error_flag[1] > 0x30000000;  // granule tags (epoch numbers) are 32-bit: start over in time
-        if (ncl > c->cl_cap || wrap) {
-            HIPCHK(hipStreamSynchronize(c->stream));
-            const int cap = ncl > c->cl_cap ? ncl : c->cl_cap;
-            if (c->cl_part) HIPCHK(hipFree(c->cl_part));
-            if (c->cl_state) HIPCHK(hipFree(c->cl_state));
-            c->cl_part = nullptr; c->cl_state = nullptr; c->cl_cap = 0;
-            HIPCHK(hipMalloc(&c->cl_part, (size_t)cap * kClusterSlotDoubles * sizeof(double)));
-            HIPCHK(hipMalloc(&c->cl_state, (size_t)cap * sizeof(unsigned int)));
-            HIPCHK(hipMemsetAsync(c->cl_part, 0, (size_t)cap * kClusterSlotDoubles * sizeof(double), c->stream));
-            HIPCHK(hipMemsetAsync(c->cl_state, 0, (size_t)cap * sizeof(unsigned int), c->stream));
-            c->error_flag[1] = 0;
-            c->cl_cap = cap;
+        const bool wrap = c->lane->error_flag[1] > 0x30000000;  // granule tags (epoch numbers) are 32-bit: start over in time
+        if (ncl > c->lane->cl_cap || wrap) {
+            HIPCHK(hipStreamSynchronize(c->lane->stream));
+            const int cap = ncl > c->lane->cl_cap ? ncl : c->lane->cl_cap;
+            if (c->lane->cl_part) HIPCHK(hipFree(c->lane->cl_part));
+            if (c->lane->cl_state) HIPCHK(hipFree(c->lane->cl_state));
+            c->lane->cl_part = nullptr; c->lane->cl_state = nullptr; c->lane->cl_cap = 0;
+            HIPCHK(hipMalloc(&c->lane->cl_part, (size_t)cap * kClusterSlotDoubles * sizeof(double)));
+            HIPCHK(hipMalloc(&c->lane->cl_state, (size_t)cap * sizeof(unsigned int)));
+            HIPCHK(hipMemsetAsync(c->lane->cl_part, 0, (size_t)cap * kClusterSlotDoubles * sizeof(double), c->lane->stream));
+            HIPCHK(hipMemsetAsync(c->lane->cl_state, 0, (size_t)cap * sizeof(unsigned int), c->lane->stream));
+            c->lane->error_flag[1] = 0;
+            c->lane->cl_cap = cap;
         }
-        a.cl_part = c->cl_part;
-        a.cl_state = c->cl_state;
+        a.cl_part = c->lane->cl_part;
+        a.cl_state = c->lane->cl_state;
         // XCD-local clusters (muse_kernels.hip) for the elementwise models, whose members meet in scalar exchanges only:
         // 22.2 -> 21.3 us at 64 sims split 4, noise_1e6 1.555 -> 1.52 ms.  The stencil model, whose members also stream
         // each other's boundary elements, measured slower with all of a cluster's traffic in one XCD (2.35 -> 2.47 ms).
@@ -399,21 +403,20 @@ static int launch_batch(muse_ctx* c, BatchArgs& a) {
         if (grid > a.nproblems) grid = a.nproblems;
         if (grid < 1) grid = 1;
     }
-    a.error_flag = c->error_flag;
     a.scratch_stride = place_scratch_vectors(pl) * c->ld;
     int rc = ensure_scratch(c, (size_t)(place_is_cluster(pl) ? a.nclusters : grid) * a.scratch_stride);
     if (rc) return rc;
-    a.scratch = c->scratch;
+    a.scratch = c->lane->scratch;
     const size_t lds = place_lds(c, pl);
     // Tickets: a workgroup's first problem is its own index, every further one a ticket (problem grid + ticket), and
     // every workgroup draws exactly one ticket past the batch, so a launch advances the counter by exactly
     // (nproblems - grid) + grid = nproblems (grid <= nproblems) -- no per-launch memset.  Wrap-around: reset explicitly.
-    if (c->ticket_base > 0x70000000u) {
-        HIPCHK(hipMemsetAsync(c->counter, 0, 16, c->stream));
-        c->ticket_base = 0;
+    if (c->lane->ticket_base > 0x70000000u) {
+        HIPCHK(hipMemsetAsync(c->lane->counter, 0, 16, c->lane->stream));
+        c->lane->ticket_base = 0;
     }
-    a.ticket_base = (int)c->ticket_base;
-    if (!place_is_cluster(pl)) c->ticket_base += (unsigned)a.nproblems;  // clusters draw no tickets
+    a.ticket_base = (int)c->lane->ticket_base;
+    if (!place_is_cluster(pl)) c->lane->ticket_base += (unsigned)a.nproblems;  // clusters draw no tickets
     hipEvent_t e0 = c->ev0, e1 = c->ev1;
     if (c->prof_on && (size_t)(2 * c->prof_count + 1) < c->prof_ev.size()) {
         e0 = c->prof_ev[2 * c->prof_count];
@@ -421,20 +424,19 @@ static int launch_batch(muse_ctx* c, BatchArgs& a) {
         c->prof_count += 1;
     }
     const bool timed = c->timing || c->prof_on;
-    if (timed) HIPCHK(hipEventRecord(e0, c->stream));
+    if (timed) HIPCHK(hipEventRecord(e0, c->lane->stream));
     {
         LaunchShape shape;
         shape.model = c->model; shape.ntheta = c->ntheta; shape.place = pl; shape.grid = grid; shape.implicit = implicit; shape.lds = lds;
         shape.big = tier_big(c, pl, a.nmaps);
         shape.lds_s = !implicit && pl == P_C256 && stencil_lds_s(c, a.csize);
-        shape.done_event = c->launch_done;
-        c->launch_done_used = c->launch_done != nullptr;
-        const hipError_t e = launch_solver(shape, a, c->stream);
+        shape.done_event = done;
+        const hipError_t e = launch_solver(shape, a, c->lane->stream);
         if (e != hipSuccess) rc = fail(MUSE_ERR_HIP, std::string("solver launch: ") + hipGetErrorString(e));
     }
     if (rc) return rc;
     if (timed) {
-        HIPCHK(hipEventRecord(e1, c->stream));
+        HIPCHK(hipEventRecord(e1, c->lane->stream));
         c->last0 = e0;
         c->last1 = e1;
         c->ev_valid = true;
@@ -442,41 +444,47 @@ static int launch_batch(muse_ctx* c, BatchArgs& a) {
     return MUSE_OK;
 }
 
-// Swap lane `l` into the context's launch-state fields (and the current one back into its slot); a lane's stream, ticket
-// counter and error word are created on first use.
+// A lane's stream, ticket counter and error word; the rest of its state grows on demand (ensure_zhat, ensure_scratch, launch_batch).
+// Lane 0 runs on the context's own stream (until muse_set_stream gives it another), lanes 1-3 on one of their own.
+static int create_lane(muse_ctx* c, int l) {
+    LaneState& ln = c->lanes[l];
+    if (ln.ready) return MUSE_OK;
+    if (l == 0) ln.stream = c->own_stream;
+    else HIPCHK(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
+    HIPCHK(hipMalloc(&ln.counter, 16));
+    HIPCHK(hipMemset(ln.counter, 0, 16));
+    HIPCHK(hipHostMalloc(&ln.error_flag, 64, hipHostMallocDefault));
+    ln.error_flag[0] = ln.error_flag[1] = 0;
+    ln.ready = true;
+    return MUSE_OK;
+}
+static void free_lane(muse_ctx* c, int l) {
+    LaneState& ln = c->lanes[l];
+    if (!ln.ready) return;
+    hipFree(ln.scratch); hipFree(ln.counter); hipFree(ln.cl_part); hipFree(ln.cl_state); hipHostFree(ln.error_flag);
+    hipFree(ln.zhat);
+    if (l != 0) hipStreamDestroy(ln.stream);   // (lane 0's is the context's own or the caller's)
+    ln = LaneState();
+}
+// The calls that follow work on lane `l` (created on first use).
 static int use_lane(muse_ctx* c, int l) {
-    if (l == c->cur_lane) return MUSE_OK;
-    LaneState& out = c->lanes[c->cur_lane];
-    out.stream = c->stream; out.scratch = c->scratch; out.scratch_doubles = c->scratch_doubles; out.counter = c->counter;
-    out.ticket_base = c->ticket_base; out.cl_part = c->cl_part; out.cl_state = c->cl_state; out.cl_cap = c->cl_cap;
-    out.error_flag = c->error_flag; out.zhat = c->zhat; out.zhat_slots = c->zhat_slots; out.ready = true;
-    LaneState& in = c->lanes[l];
-    if (!in.ready) {
-        HIPCHK(hipStreamCreateWithFlags(&in.stream, hipStreamNonBlocking));
-        HIPCHK(hipMalloc(&in.counter, 16));
-        HIPCHK(hipMemset(in.counter, 0, 16));
-        HIPCHK(hipHostMalloc(&in.error_flag, 64, hipHostMallocDefault));
-        in.error_flag[0] = in.error_flag[1] = 0;
-        in.ready = true;
-    }
-    c->stream = in.stream; c->scratch = in.scratch; c->scratch_doubles = in.scratch_doubles; c->counter = in.counter;
-    c->ticket_base = in.ticket_base; c->cl_part = in.cl_part; c->cl_state = in.cl_state; c->cl_cap = in.cl_cap;
-    c->error_flag = in.error_flag;
-    c->zhat = in.zhat;
-    c->zhat_slots = in.zhat_slots;
-    c->cur_lane = l;
+    const int rc = create_lane(c, l);
+    if (rc) return rc;
+    c->lane = &c->lanes[l];
     return MUSE_OK;
 }
 template <class F>
-static int for_each_lane(muse_ctx* c, F&& f) {   // f() with every lane that exists swapped in; lane 0 afterwards
+static int for_each_lane(muse_ctx* c, F&& f) {   // f(lane) for every lane that exists, until one fails
     int rc = MUSE_OK;
-    for (int l = 0; l < kMaxLanes && rc == MUSE_OK; ++l) {
-        if (l != c->cur_lane && !c->lanes[l].ready) continue;
-        rc = use_lane(c, l);
-        if (rc == MUSE_OK) rc = f();
-    }
-    const int rc0 = use_lane(c, 0);
-    return rc ? rc : rc0;
+    for (int l = 0; l < kMaxLanes && rc == MUSE_OK; ++l)
+        if (c->lanes[l].ready) rc = f(c->lanes[l]);
+    return rc;
+}
+static int drain_lanes(muse_ctx* c) {
+    return for_each_lane(c, [](LaneState& ln) -> int {
+        HIPCHK(hipStreamSynchronize(ln.stream));
+        return MUSE_OK;
+    });
 }
 
 // A result area that is launched again (or whose pinned block an FD / implicit-diff map is about to reuse: those are
@@ -485,10 +493,7 @@ static int for_each_lane(muse_ctx* c, F&& f) {   // f() with every lane that exi
 // lane.  Drain every lane first (never taken by a caller that waits for an area before launching on it again).
 static int settle_area(muse_ctx* c, int area) {
     if (!c->area_inflight[area] || c->nlanes <= 1) return MUSE_OK;
-    return for_each_lane(c, [&]() -> int {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        return MUSE_OK;
-    });
+    return drain_lanes(c);
 }
 
 #if defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_NCONST)
@@ -606,14 +611,13 @@ int muse_ctx_create(int model, int64_t N, int ntheta, int device, muse_ctx** out
         }
     }
     HIPCHK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
-    c->stream = c->own_stream;
+    {
+        const int rc = use_lane(c, 0);
+        if (rc) return rc;
+    }
     HIPCHK(hipMalloc(&c->x_data, (size_t)c->ld * sizeof(double)));
-    HIPCHK(hipMalloc(&c->counter, 16));
-    HIPCHK(hipMemset(c->counter, 0, 16));
     HIPCHK(hipMalloc(&c->fid_flag, 64));
     HIPCHK(hipMemset(c->fid_flag, 0, 64));
-    HIPCHK(hipHostMalloc(&c->error_flag, 64, hipHostMallocDefault));
-    c->error_flag[0] = c->error_flag[1] = 0;
     HIPCHK(hipHostMalloc(&c->clock_pin, 64, hipHostMallocDefault));
     memset(c->clock_pin, 0, 64);
     HIPCHK(hipMalloc(&c->tmp, (size_t)3 * c->ld * sizeof(double)));
@@ -621,9 +625,9 @@ int muse_ctx_create(int model, int64_t N, int ntheta, int device, muse_ctx** out
     HIPCHK(hipEventCreate(&c->ev0));
     HIPCHK(hipEventCreate(&c->ev1));
     for (int r = 0; r < kResultAreas; ++r) HIPCHK(hipEventCreateWithFlags(&c->area_done[r], hipEventDisableTiming));
-    HIPCHK(hipMemsetAsync(c->x_data, 0, (size_t)c->ld * sizeof(double), c->stream));
-    HIPCHK(hipMemsetAsync(c->tmp, 0, (size_t)3 * c->ld * sizeof(double), c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemsetAsync(c->x_data, 0, (size_t)c->ld * sizeof(double), c->lane->stream));
+    HIPCHK(hipMemsetAsync(c->tmp, 0, (size_t)3 * c->ld * sizeof(double), c->lane->stream));
+    HIPCHK(hipStreamSynchronize(c->lane->stream));
     *out = c;
     return MUSE_OK;
 }
@@ -637,11 +641,9 @@ int muse_ctx_comm_slot(muse_ctx* c, void*** comm, int* device, void** stream) {
     if (!c) return fail(MUSE_ERR_INVALID, "ctx is NULL");
     // the communicator's stream order (RCCL transport: collective stream <- event on the solver's stream) is tied to lane 0:
     // hand out lane 0's stream whatever lane the last map used
-    const int rc = use_lane(c, 0);
-    if (rc) return rc;
     *comm = &c->comm;
     *device = c->device;
-    *stream = (void*)c->stream;
+    *stream = (void*)c->lanes[0].stream;
     return MUSE_OK;
 }
 int muse_ctx_switches(muse_ctx* c, const Switches** sw, int* debug) {
@@ -677,17 +679,11 @@ int muse_ctx_comm_buffer(muse_ctx* c, size_t doubles, double** buf) {
 int muse_ctx_destroy(muse_ctx* c) {
     if (!c) return MUSE_OK;
     hipSetDevice(c->device);
-    (void)for_each_lane(c, [&]() { hipStreamSynchronize(c->stream); return MUSE_OK; });
-    for (int l = 1; l < kMaxLanes; ++l) {   // lane 0's resources are the context's own fields now (freed below)
-        LaneState& ln = c->lanes[l];
-        if (!ln.ready) continue;
-        hipFree(ln.scratch); hipFree(ln.counter); hipFree(ln.cl_part); hipFree(ln.cl_state); hipHostFree(ln.error_flag);
-        hipFree(ln.zhat);
-        hipStreamDestroy(ln.stream);
-    }
+    (void)for_each_lane(c, [](LaneState& ln) { hipStreamSynchronize(ln.stream); return MUSE_OK; });
     muse_comm_destroy(c);
     free_run_buffers(c);
-    hipFree(c->cl_part); hipFree(c->cl_state); hipHostFree(c->error_flag); hipHostFree(c->clock_pin);
+    for (int l = 0; l < kMaxLanes; ++l) free_lane(c, l);
+    hipHostFree(c->clock_pin);
     hipFree(c->ncache);
     for (int k = 0; k < 4; ++k) {
         if (c->consts_dev[k]) hipFree(c->consts_dev[k]);
@@ -699,7 +695,7 @@ int muse_ctx_destroy(muse_ctx* c) {
         for (int k = 0; k < MUSE_MODEL_MAX_CONST; ++k) { muse_host_consts[k] = nullptr; muse_host_const_len[k] = 0; }
     }
 #endif
-    hipFree(c->x_data); hipFree(c->zhat); hipFree(c->scratch); hipFree(c->counter); hipFree(c->fid_flag); hipFree(c->fid_norm); hipFree(c->tmp);
+    hipFree(c->x_data); hipFree(c->fid_flag); hipFree(c->fid_norm); hipFree(c->tmp);
     hipFree(c->small_dev); if (c->tsample_dev) hipFree(c->tsample_dev); if (c->tsample_pin) hipHostFree(c->tsample_pin);
     if (c->comm_buf) hipFree(c->comm_buf);
     for (int r = 0; r < kResultAreas; ++r) {
@@ -716,8 +712,7 @@ int muse_ctx_destroy(muse_ctx* c) {
 static int check_ctx(muse_ctx* c) {
     if (!c) return fail(MUSE_ERR_INVALID, "ctx is NULL");
     HIPCHK(hipSetDevice(c->device));
-    const int rc = use_lane(c, 0);   // every entry point works on lane 0 unless it says otherwise (map_async_impl)
-    if (rc) return rc;
+    c->lane = &c->lanes[0];          // every entry point works on lane 0 unless it says otherwise (map_async_impl)
     MUSE_OWN_CONSTANTS(c);           // (a user model's run-time constants: this context's, if another one installed its own since)
     return MUSE_OK;
 }
@@ -728,16 +723,16 @@ int muse_set_data(muse_ctx* c, const double* x, int mem) {
     int rc = check_ctx(c);
     if (rc) return rc;
     if (!x) return fail(MUSE_ERR_INVALID, "x is NULL");
-    HIPCHK(hipMemcpyAsync(c->x_data, x, (size_t)c->N * sizeof(double), in_kind(mem), c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpyAsync(c->x_data, x, (size_t)c->N * sizeof(double), in_kind(mem), c->lane->stream));
+    HIPCHK(hipStreamSynchronize(c->lane->stream));
     c->has_data = true;
     return MUSE_OK;
 }
 int muse_set_stream(muse_ctx* c, void* s) {
     int rc = check_ctx(c);
     if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->stream = s ? (hipStream_t)s : c->own_stream;
+    HIPCHK(hipStreamSynchronize(c->lane->stream));
+    c->lane->stream = s ? (hipStream_t)s : c->own_stream;   // (lane 0's: check_ctx; the other lanes keep their own)
     return MUSE_OK;
 }
 int muse_set_placement(muse_ctx* c, int placement) {
@@ -764,19 +759,19 @@ int muse_set_element_split(muse_ctx* c, int split) {
 // 32-bit wrap), and mark every result area whose launch was in flight as failed -- each of their waits reports the error
 // once -- before the flag is cleared.
 static int check_error_flag(muse_ctx* c) {
-    bool any = *c->error_flag != 0;
-    for (int l = 0; l < kMaxLanes; ++l)
-        if (l != c->cur_lane && c->lanes[l].ready && c->lanes[l].error_flag[0]) any = true;
+    bool any = false;
+    for (const LaneState& ln : c->lanes)
+        if (ln.ready && ln.error_flag[0]) any = true;
     if (!any) return MUSE_OK;
-    (void)for_each_lane(c, [&]() -> int {
-        (void)hipStreamSynchronize(c->stream);
-        if (c->cl_part && c->cl_cap > 0) {
-            (void)hipMemsetAsync(c->cl_part, 0, (size_t)c->cl_cap * kClusterSlotDoubles * sizeof(double), c->stream);
-            (void)hipMemsetAsync(c->cl_state, 0, (size_t)c->cl_cap * sizeof(unsigned int), c->stream);
-            (void)hipStreamSynchronize(c->stream);
+    (void)for_each_lane(c, [](LaneState& ln) -> int {
+        (void)hipStreamSynchronize(ln.stream);
+        if (ln.cl_part && ln.cl_cap > 0) {
+            (void)hipMemsetAsync(ln.cl_part, 0, (size_t)ln.cl_cap * kClusterSlotDoubles * sizeof(double), ln.stream);
+            (void)hipMemsetAsync(ln.cl_state, 0, (size_t)ln.cl_cap * sizeof(unsigned int), ln.stream);
+            (void)hipStreamSynchronize(ln.stream);
         }
-        c->error_flag[1] = 0;
-        c->error_flag[0] = 0;
+        ln.error_flag[1] = 0;
+        ln.error_flag[0] = 0;
         return MUSE_OK;
     });
     for (int r = 0; r < kResultAreas; ++r) {
@@ -802,10 +797,7 @@ int muse_placement_info(muse_ctx* c, int* threads, int* workgroups_per_element, 
 int muse_synchronize(muse_ctx* c) {
     int rc = check_ctx(c);
     if (rc) return rc;
-    return for_each_lane(c, [&]() -> int {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        return MUSE_OK;
-    });
+    return drain_lanes(c);
 }
 int muse_set_constants(muse_ctx* c, int k, const double* values, int64_t count, int mem) {
 #if defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_NCONST)
@@ -820,10 +812,10 @@ int muse_set_constants(muse_ctx* c, int k, const double* values, int64_t count, 
         c->consts_host[k] = (double*)malloc((size_t)count * sizeof(double));
         if (!c->consts_host[k]) return fail(MUSE_ERR_ALLOC, "malloc(constants) failed");
     }
-    HIPCHK(hipMemcpyAsync(c->consts_dev[k], values, (size_t)count * sizeof(double), in_kind(mem), c->stream));
+    HIPCHK(hipMemcpyAsync(c->consts_dev[k], values, (size_t)count * sizeof(double), in_kind(mem), c->lane->stream));
     HIPCHK(hipMemcpyAsync(c->consts_host[k], values, (size_t)count * sizeof(double),
-                          mem == MUSE_MEM_DEVICE ? hipMemcpyDeviceToHost : hipMemcpyHostToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+                          mem == MUSE_MEM_DEVICE ? hipMemcpyDeviceToHost : hipMemcpyHostToHost, c->lane->stream));
+    HIPCHK(hipStreamSynchronize(c->lane->stream));
     for (int64_t i = 0; i < count; ++i)
         if (!isfinite(c->consts_host[k][i])) {
             c->consts_len[k] = 0;
@@ -921,7 +913,7 @@ int muse_debug_stamps(muse_ctx* c, int64_t nproblems, unsigned long long* out) {
         c->stamps_cap = nproblems;
         return MUSE_OK;
     }
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipStreamSynchronize(c->lane->stream));
     HIPCHK(hipMemcpy(out, c->stamps, (size_t)nproblems * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return MUSE_OK;
 }
@@ -944,7 +936,7 @@ int muse_profile_begin(muse_ctx* c, int max_launches) {
     int rc = check_ctx(c);
     if (rc) return rc;
     if (max_launches < 1 || max_launches > 65536) return fail(MUSE_ERR_INVALID, "max_launches out of range");
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipStreamSynchronize(c->lane->stream));
     while (c->prof_ev.size() < (size_t)(2 * max_launches + 2)) {
         hipEvent_t e;
         HIPCHK(hipEventCreate(&e));
@@ -958,10 +950,7 @@ int muse_profile_end(muse_ctx* c, float* ms_out, int cap, int* count) {
     int rc = check_ctx(c);
     if (rc) return rc;
     if (!count) return fail(MUSE_ERR_INVALID, "count is NULL");
-    rc = for_each_lane(c, [&]() -> int {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        return MUSE_OK;
-    });
+    rc = drain_lanes(c);
     if (rc) return rc;
     c->prof_on = false;
     *count = c->prof_count;
@@ -974,7 +963,7 @@ int muse_profile_clock_hz(muse_ctx* c, double* hz_out) {
     int rc = check_ctx(c);
     if (rc) return rc;
     if (!hz_out) return fail(MUSE_ERR_INVALID, "hz_out is NULL");
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipStreamSynchronize(c->lane->stream));
     const unsigned long long* t = c->clock_pin;
     if (t[3] <= t[1] || t[2] <= t[0]) return fail(MUSE_ERR_INVALID, "no profiled launch has run (muse_profile_begin ... end)");
     *hz_out = (double)(t[2] - t[0]) / (double)(t[3] - t[1]) * 1e8;  // s_memrealtime ticks at a constant 100 MHz
@@ -1013,10 +1002,10 @@ int muse_sample_x_z(muse_ctx* c, uint64_t seed, int64_t sim, const double* theta
     base_args(c, a, theta);
     a.seed = seed;
     double *dx = c->tmp, *dz = c->tmp + c->ld, *dn = c->tmp + 2 * c->ld;
-    HIPCHK(launch_sample(c->model, a, (uint64_t)sim, dx, dz, dn, c->stream));
-    if (x_out) HIPCHK(hipMemcpyAsync(x_out, dx, (size_t)c->N * sizeof(double), out_kind(mem), c->stream));
-    if (z_out) HIPCHK(hipMemcpyAsync(z_out, dz, (size_t)c->N * sizeof(double), out_kind(mem), c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(launch_sample(c->model, a, (uint64_t)sim, dx, dz, dn, c->lane->stream));
+    if (x_out) HIPCHK(hipMemcpyAsync(x_out, dx, (size_t)c->N * sizeof(double), out_kind(mem), c->lane->stream));
+    if (z_out) HIPCHK(hipMemcpyAsync(z_out, dz, (size_t)c->N * sizeof(double), out_kind(mem), c->lane->stream));
+    HIPCHK(hipStreamSynchronize(c->lane->stream));
     return MUSE_OK;
 }
 
@@ -1024,9 +1013,9 @@ static int run_loglike(muse_ctx* c, const double* x, const double* z, const doub
     BatchArgs a;
     base_args(c, a, theta);
     double *dx = c->tmp, *dz = c->tmp + c->ld;
-    HIPCHK(hipMemcpyAsync(dx, x, (size_t)c->N * sizeof(double), in_kind(mem), c->stream));
-    HIPCHK(hipMemcpyAsync(dz, z, (size_t)c->N * sizeof(double), in_kind(mem), c->stream));
-    HIPCHK(launch_loglike(c->model, a, dx, dz, gdev, c->small_dev, c->stream));
+    HIPCHK(hipMemcpyAsync(dx, x, (size_t)c->N * sizeof(double), in_kind(mem), c->lane->stream));
+    HIPCHK(hipMemcpyAsync(dz, z, (size_t)c->N * sizeof(double), in_kind(mem), c->lane->stream));
+    HIPCHK(launch_loglike(c->model, a, dx, dz, gdev, c->small_dev, c->lane->stream));
     return MUSE_OK;
 }
 
@@ -1039,9 +1028,9 @@ int muse_logLike_and_grad_z(muse_ctx* c, const double* x, const double* z, const
     rc = run_loglike(c, x, z, theta, grad_out ? gdev : nullptr, mem);
     if (rc) return rc;
     double small[1 + kBigTheta];
-    HIPCHK(hipMemcpyAsync(small, c->small_dev, sizeof(small), hipMemcpyDeviceToHost, c->stream));
-    if (grad_out) HIPCHK(hipMemcpyAsync(grad_out, gdev, (size_t)c->N * sizeof(double), out_kind(mem), c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpyAsync(small, c->small_dev, sizeof(small), hipMemcpyDeviceToHost, c->lane->stream));
+    if (grad_out) HIPCHK(hipMemcpyAsync(grad_out, gdev, (size_t)c->N * sizeof(double), out_kind(mem), c->lane->stream));
+    HIPCHK(hipStreamSynchronize(c->lane->stream));
     if (logLike_out) *logLike_out = small[0];
     return MUSE_OK;
 }
@@ -1053,8 +1042,8 @@ int muse_grad_theta(muse_ctx* c, const double* x, const double* z, const double*
     rc = run_loglike(c, x, z, theta, nullptr, mem);
     if (rc) return rc;
     double small[1 + kBigTheta];
-    HIPCHK(hipMemcpyAsync(small, c->small_dev, sizeof(small), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpyAsync(small, c->small_dev, sizeof(small), hipMemcpyDeviceToHost, c->lane->stream));
+    HIPCHK(hipStreamSynchronize(c->lane->stream));
     for (int k = 0; k < c->ntheta; ++k) g_out[k] = small[1 + k];
     return MUSE_OK;
 }
@@ -1066,7 +1055,7 @@ static int enqueue_results_copy(muse_ctx* c, int area, int64_t n) {
     // launches (measured: 51.5 vs 54.3 us per 512-sim step), but the results then have to leave with system-scope
     // stores, and with those in flight hipLaunchKernel was measured to block for ~40 us per call: not kept.
     c->res_n[area] = n;
-    HIPCHK(hipEventRecord(c->area_done[area], c->stream));
+    HIPCHK(hipEventRecord(c->area_done[area], c->lane->stream));
     return MUSE_OK;
 }
 
@@ -1076,7 +1065,7 @@ int muse_zhat_at_theta(muse_ctx* c, const double* x, const double* z0, const dou
     if (rc) return rc;
     if (!x || !z0 || !theta || !z_out) return fail(MUSE_ERR_INVALID, "NULL argument");
     // the single-element solve uses a private zhat slot after the batch slots
-    rc = ensure_zhat(c, c->zhat_slots > 0 ? c->zhat_slots : 1);
+    rc = ensure_zhat(c, c->lane->zhat_slots > 0 ? c->lane->zhat_slots : 1);
     if (rc) return rc;
     rc = ensure_results(c, kResultAreas - 1, 1);
     if (rc) return rc;
@@ -1090,18 +1079,18 @@ int muse_zhat_at_theta(muse_ctx* c, const double* x, const double* z0, const dou
     a.slot0 = 0;
     double* dx = c->tmp;
     double* dz = c->tmp + c->ld;
-    HIPCHK(hipMemcpyAsync(dx, x, (size_t)c->N * sizeof(double), in_kind(mem), c->stream));
-    HIPCHK(hipMemcpyAsync(dz, z0, (size_t)c->N * sizeof(double), in_kind(mem), c->stream));
+    HIPCHK(hipMemcpyAsync(dx, x, (size_t)c->N * sizeof(double), in_kind(mem), c->lane->stream));
+    HIPCHK(hipMemcpyAsync(dz, z0, (size_t)c->N * sizeof(double), in_kind(mem), c->lane->stream));
     a.x_given = dx;
     a.scores = c->scores_dev[kResultAreas - 1];
     a.info = c->info_dev[kResultAreas - 1];
     a.zhat = dz;  // the element's z lives in the tmp vector (slot 0 of a one-slot view), not in the batch slots
     rc = launch_batch(c, a);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(z_out, dz, (size_t)c->N * sizeof(double), out_kind(mem), c->stream));
+    HIPCHK(hipMemcpyAsync(z_out, dz, (size_t)c->N * sizeof(double), out_kind(mem), c->lane->stream));
     rc = enqueue_results_copy(c, kResultAreas - 1, 1);
     if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipStreamSynchronize(c->lane->stream));
     rc = check_error_flag(c);
     if (rc) return rc;
     if (info) *info = c->info_pin[kResultAreas - 1][0];
@@ -1146,6 +1135,10 @@ static int map_async_impl(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t
         rc = use_lane(c, area % c->nlanes);
         if (rc) return rc;
     }
+    struct BackToLane0 {   // whichever way this function returns: no entry point leaves another lane current
+        muse_ctx* c;
+        ~BackToLane0() { c->lane = &c->lanes[0]; }
+    } back_to_lane0{c};
     const int64_t total = n * o.nmaps, rows = stride * o.nmaps;
     if (total > 0x7fffffff || rows > 0x7fffffff) return fail(MUSE_ERR_INVALID, "batch too large");
     rc = ensure_zhat(c, total);
@@ -1175,53 +1168,37 @@ static int map_async_impl(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t
         }
     const int64_t nsim = sim_end - sim_begin;
     if (o.ncache_mode != 0) {   // the caller (muse_run) says which: store with the first iteration, load with the later ones
-        if (o.nmaps == 1 && nsim > 0 && o.ncache_mode == 2 && ncache_holds(c, seed, sim_begin, nsim)) {
-            a.ncache = c->ncache;
-            a.ncache_sim0 = c->nc_sim0;
-            a.ncache_count = (int)c->nc_count;
-            a.ncache_mode = 2;
-        } else if (o.nmaps == 1 && nsim > 0 && o.ncache_mode == 1 && ensure_ncache(c, nsim)) {
-            a.ncache = c->ncache;
-            a.ncache_sim0 = sim_begin;
-            a.ncache_count = (int)nsim;
-            a.ncache_mode = 1;
-        }
-    } else if (o.ncache_mode == 0 && c->nc_auto && o.nmaps == 1 && nsim > 0 && c->cur_lane == 0 && ncache_applies(c)) {
+        if (o.nmaps == 1 && nsim > 0 && o.ncache_mode == 2 && ncache_holds(c, seed, sim_begin, nsim))
+            attach_ncache(a, c->ncache, c->nc_sim0, c->nc_count, 2);
+        else if (o.nmaps == 1 && nsim > 0 && o.ncache_mode == 1 && ensure_ncache(c, nsim))
+            attach_ncache(a, c->ncache, sim_begin, nsim, 1);
+    } else if (o.ncache_mode == 0 && c->nc_auto && o.nmaps == 1 && nsim > 0 && c->lane == &c->lanes[0] && ncache_applies(c)) {
         // A map over simulations the context has drawn before -- every iteration of a muse! loop the HOST drives (muse.py:
         // the same streams at a new theta, src/muse.jl:134,169), a get_J! pass after it: the second time a range is asked
         // for its normals are stored beside the solve, from the third time on they are loaded instead of generated (the
         // same doubles: bit-identical results).  Lane 0 only: stream order is what puts the storing launch before the
         // loading ones.  A map that never repeats (the pipelined cold steps of bench.py) stores nothing.
         const int64_t budget = (int64_t)c->sw.ncache_max_bytes;
-        if (ncache_holds(c, seed, sim_begin, nsim)) {
-            a.ncache = c->ncache;
-            a.ncache_sim0 = c->nc_sim0;
-            a.ncache_count = (int)c->nc_count;
-            a.ncache_mode = 2;
-        } else if (c->nc_seen_count == nsim && c->nc_seen_seed == seed && c->nc_seen_sim0 == sim_begin &&
-                   nsim * 2 * c->ld * (int64_t)sizeof(double) <= budget && ensure_ncache(c, nsim)) {
-            a.ncache = c->ncache;
-            a.ncache_sim0 = sim_begin;
-            a.ncache_count = (int)nsim;
-            a.ncache_mode = 1;
-        }
+        if (ncache_holds(c, seed, sim_begin, nsim))
+            attach_ncache(a, c->ncache, c->nc_sim0, c->nc_count, 2);
+        else if (c->nc_seen_count == nsim && c->nc_seen_seed == seed && c->nc_seen_sim0 == sim_begin &&
+                 nsim * 2 * c->ld * (int64_t)sizeof(double) <= budget && ensure_ncache(c, nsim))
+            attach_ncache(a, c->ncache, sim_begin, nsim, 1);
         c->nc_seen_seed = seed; c->nc_seen_sim0 = sim_begin; c->nc_seen_count = nsim;
     }
     // the area's completion event is signalled by this launch itself; with timing events around the launch (profiling)
     // the plain record after it keeps the order start, kernel, stop, done
-    c->launch_done = (c->timing || c->prof_on || c->sw.no_ext_launch) ? nullptr : c->area_done[area];
-    c->launch_done_used = false;
+    const hipEvent_t done = (c->timing || c->prof_on || c->sw.no_ext_launch) ? nullptr : c->area_done[area];
     // A storing launch overwrites the cache: whatever it held is gone the moment the launch is issued, and the new range is
     // claimed only once the launch HAS been issued -- a launch that fails leaves no tag behind under which a later map would
     // load slots that were never written (a launch that is issued and then raises the error word: check_error_flag).
     if (a.ncache_mode == 1) c->nc_count = 0;
-    rc = launch_batch(c, a);
-    c->launch_done = nullptr;
+    rc = launch_batch(c, a, done);
     if (rc) return rc;
     if (a.ncache_mode == 1) { c->nc_seed = seed; c->nc_sim0 = sim_begin; c->nc_count = nsim; }
     c->area_inflight[area] = true;
     c->res_rows[area] = rows;
-    if (c->launch_done_used) {
+    if (done) {
         c->res_n[area] = total;
         return MUSE_OK;
     }
@@ -1266,12 +1243,12 @@ int muse_wait_event(void* event) {
 // the same for everything enqueued on the context's stream
 static int muse_wait_event_or_stream(muse_ctx* c) {
     for (int spin = 0; spin < 4000000; ++spin) {
-        const hipError_t e = hipStreamQuery(c->stream);
+        const hipError_t e = hipStreamQuery(c->lane->stream);
         if (e == hipSuccess) return MUSE_OK;
         if (e != hipErrorNotReady) return fail(MUSE_ERR_HIP, std::string("hipStreamQuery: ") + hipGetErrorString(e));
         MUSE_CPU_RELAX();
     }
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipStreamSynchronize(c->lane->stream));
     return MUSE_OK;
 }
 
@@ -1420,7 +1397,7 @@ static int ensure_run_buffers(muse_ctx* c, int maxsteps, int S, int64_t nlocal, 
     RunBuffers& r = *c->run;
     const int nt = c->ntheta;
     if (nlocal * nt > r.scores_dummy_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipStreamSynchronize(c->lane->stream));
         if (r.scores_dummy) HIPCHK(hipFree(r.scores_dummy));
         r.scores_dummy = nullptr; r.scores_dummy_cap = 0;
         HIPCHK(hipMalloc(&r.scores_dummy, (size_t)(nlocal * nt) * sizeof(double)));
@@ -1432,18 +1409,18 @@ static int ensure_run_buffers(muse_ctx* c, int maxsteps, int S, int64_t nlocal, 
     }
     const int64_t ngran = (int64_t)2 * nt * (S + 1) + 2 * (kMaxTheta + 1);   // the scores, then the stepper's theta and status
     if (ngran > r.gran_cap || r.tag > 0x70000000u) {
-        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipStreamSynchronize(c->lane->stream));
         if (ngran > r.gran_cap) {
             if (r.gran) HIPCHK(hipFree(r.gran));
             r.gran = nullptr; r.gran_cap = 0;
             HIPCHK(hipMalloc(&r.gran, (size_t)ngran * sizeof(unsigned long long)));
             r.gran_cap = ngran;
         }
-        HIPCHK(hipMemsetAsync(r.gran, 0, (size_t)r.gran_cap * sizeof(unsigned long long), c->stream));  // tag 0 is never used
+        HIPCHK(hipMemsetAsync(r.gran, 0, (size_t)r.gran_cap * sizeof(unsigned long long), c->lane->stream));  // tag 0 is never used
         r.tag = 0;
     }
     if (nlocal > r.info_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipStreamSynchronize(c->lane->stream));
         if (r.info_dummy) HIPCHK(hipFree(r.info_dummy));
         r.info_dummy = nullptr; r.info_cap = 0;
         HIPCHK(hipMalloc(&r.info_dummy, (size_t)nlocal * sizeof(muse_info)));
@@ -1452,21 +1429,21 @@ static int ensure_run_buffers(muse_ctx* c, int maxsteps, int S, int64_t nlocal, 
     const int64_t nh = (int64_t)maxsteps * MUSE_RUN_HIST(kMaxTheta), ns = (int64_t)maxsteps * (S + 1) * nt,
                   ni = want_info ? (int64_t)maxsteps * nlocal : 0;
     if (nh > r.cap_hist) {
-        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipStreamSynchronize(c->lane->stream));
         if (r.hist) HIPCHK(hipHostFree(r.hist));
         r.hist = nullptr; r.cap_hist = 0;
         HIPCHK(hipHostMalloc(&r.hist, (size_t)nh * sizeof(double), hipHostMallocDefault));
         r.cap_hist = nh;
     }
     if (ns > r.cap_scores) {
-        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipStreamSynchronize(c->lane->stream));
         if (r.scores) HIPCHK(hipHostFree(r.scores));
         r.scores = nullptr; r.cap_scores = 0;
         HIPCHK(hipHostMalloc(&r.scores, (size_t)ns * sizeof(double), hipHostMallocDefault));
         r.cap_scores = ns;
     }
     if (ni > r.cap_infos) {
-        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipStreamSynchronize(c->lane->stream));
         if (r.infos) HIPCHK(hipHostFree(r.infos));
         r.infos = nullptr; r.cap_infos = 0;
         HIPCHK(hipHostMalloc(&r.infos, (size_t)ni * sizeof(muse_info), hipHostMallocDefault));
@@ -1599,17 +1576,12 @@ static int run_loop_launch(muse_ctx* c, uint64_t seed, const double* theta0, con
     a.store_zhat = 1;
     a.sim_begin = sim_lo;
     a.slot0 = 0;
-    a.nmaps = 1;
-    a.n_per_map = (int)nprob;
-    a.map_stride = nprob;
     bool storing = false;
     if (nsim_local > 0) {
         const bool held = ncache_holds(c, seed, sim_lo, nsim_local);   // (an earlier run, or maps of the host driver, drew these streams)
         if (held || ensure_ncache(c, nsim_local)) {
-            a.ncache = c->ncache;
-            a.ncache_sim0 = held ? c->nc_sim0 : sim_lo;
-            a.ncache_count = held ? (int)c->nc_count : (int)nsim_local;
-            a.ncache_mode = held ? 2 : 1;   // of the FIRST iteration; the later ones load
+            // (the mode of the FIRST iteration; the later ones load)
+            attach_ncache(a, c->ncache, held ? c->nc_sim0 : sim_lo, held ? c->nc_count : nsim_local, held ? 2 : 1);
             // (a storing run overwrites the cache now and claims its range when it has ENDED well: an aborted loop -- workers
             //  that never ran their first iteration, a bounded wait that expired -- must not leave a tag behind)
             storing = !held;
@@ -1624,22 +1596,8 @@ static int run_loop_launch(muse_ctx* c, uint64_t seed, const double* theta0, con
         a.ngran_peers = sh->npeers;
         for (int q = 0; q < sh->npeers; ++q) a.gran_peers[q] = sh->peers[q] + (size_t)row0 * nt * 2;
     }
-    // the common fields, as launch_batch fills them
-    a.N = c->N;
-    a.ld = c->ld;
-    a.ntheta = nt;
-    for (int k = 0; k <= kMaxTheta; ++k) {
-        a.bnd[k] = c->bnd[k];
-        a.bnd32[k] = k < nblocks_of(nt) ? (int)c->bnd[k] : 0x7fffffff;
-    }
-    a.x_data = c->x_data;
-    a.zhat = c->zhat;
-    a.work_counter = c->counter;
-    a.ticket_base = (int)c->ticket_base;   // (no tickets are drawn: elements are dealt statically)
-    a.debug = c->debug & 0xffff;   // (bits 16-21 are host-side: switches.hpp)
-    a.stamps = (c->stamps && a.nproblems + 3 <= c->stamps_cap) ? c->stamps : nullptr;   // (+3: the loop kernel's own rows)
-    a.csize = 1;
-    a.error_flag = c->error_flag;
+    common_args(c, a, a.nproblems + 3);   // (+3: the loop kernel's own rows of the stamps)
+    a.ticket_base = (int)c->lane->ticket_base;   // (no tickets are drawn: elements are dealt statically)
     // workers (each owns elements w, w + nworkers, ...) and one stepper, all resident at once
     int nworkers = max_grid - 1 < (int)nprob ? max_grid - 1 : (int)nprob;
     if (c->sw.loop_grid >= 1 && c->sw.loop_grid < nworkers) nworkers = c->sw.loop_grid;   // tuning aid (never more than what is resident at once)
@@ -1657,7 +1615,7 @@ static int run_loop_launch(muse_ctx* c, uint64_t seed, const double* theta0, con
     a.scratch_stride = place_scratch_vectors(pl) * c->ld;
     rc = ensure_scratch(c, (size_t)grid * a.scratch_stride);
     if (rc) return rc;
-    a.scratch = c->scratch;
+    a.scratch = c->lane->scratch;
     LoopArgs l;
     memset(&l, 0, sizeof l);
     step_params(c, o, l.sp);
@@ -1684,7 +1642,7 @@ static int run_loop_launch(muse_ctx* c, uint64_t seed, const double* theta0, con
         l.scores_stride = 0;
         l.scores_all_out = r.scores;
         // (this GPU's theta granules carry the board's tags: they grow with it)
-        if (r.tag > sh->tag_base) HIPCHK(hipMemsetAsync(r.gran + (size_t)2 * nt * nprob_total, 0, (size_t)2 * (kMaxTheta + 1) * sizeof(unsigned long long), c->stream));
+        if (r.tag > sh->tag_base) HIPCHK(hipMemsetAsync(r.gran + (size_t)2 * nt * nprob_total, 0, (size_t)2 * (kMaxTheta + 1) * sizeof(unsigned long long), c->lane->stream));
         if (r.tag < sh->tag_base + (unsigned)maxsteps + 1) r.tag = sh->tag_base + (unsigned)maxsteps + 1;   // (never backwards: this
                                                                   // GPU's own score granules of unsharded runs keep their last tags)
     } else {
@@ -1702,7 +1660,7 @@ static int run_loop_launch(muse_ctx* c, uint64_t seed, const double* theta0, con
     auto now_us = [] { return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count() * 1e-3; };
     const double t_a = trace ? now_us() : 0.0;
     {
-        const hipError_t e = launch_loop(shape, a, l, c->stream);
+        const hipError_t e = launch_loop(shape, a, l, c->lane->stream);
         if (e != hipSuccess) return fail(MUSE_ERR_HIP, std::string("loop kernel launch: ") + hipGetErrorString(e));
     }
     const double t_b = trace ? now_us() : 0.0;
@@ -1789,11 +1747,11 @@ int muse_internal_run_loop_shard(muse_ctx* c, uint64_t seed, const double* theta
 int muse_get_zhat(muse_ctx* c, int64_t b, int64_t e, double* out, int mem) {
     int rc = check_ctx(c);
     if (rc) return rc;
-    if (!out || b < 0 || e < b || e > c->zhat_slots) return fail(MUSE_ERR_INVALID, "bad slot range");
+    if (!out || b < 0 || e < b || e > c->lane->zhat_slots) return fail(MUSE_ERR_INVALID, "bad slot range");
     if (e == b) return MUSE_OK;
-    HIPCHK(hipMemcpy2DAsync(out, (size_t)c->N * sizeof(double), c->zhat + b * c->ld, (size_t)c->ld * sizeof(double),
-                            (size_t)c->N * sizeof(double), (size_t)(e - b), out_kind(mem), c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy2DAsync(out, (size_t)c->N * sizeof(double), c->lane->zhat + b * c->ld, (size_t)c->ld * sizeof(double),
+                            (size_t)c->N * sizeof(double), (size_t)(e - b), out_kind(mem), c->lane->stream));
+    HIPCHK(hipStreamSynchronize(c->lane->stream));
     return MUSE_OK;
 }
 int muse_set_zhat(muse_ctx* c, int64_t b, int64_t e, const double* in, int mem) {
@@ -1803,15 +1761,15 @@ int muse_set_zhat(muse_ctx* c, int64_t b, int64_t e, const double* in, int mem) 
     if (e == b) return MUSE_OK;
     rc = ensure_zhat(c, e);
     if (rc) return rc;
-    HIPCHK(hipMemcpy2DAsync(c->zhat + b * c->ld, (size_t)c->ld * sizeof(double), in, (size_t)c->N * sizeof(double),
-                            (size_t)c->N * sizeof(double), (size_t)(e - b), in_kind(mem), c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy2DAsync(c->lane->zhat + b * c->ld, (size_t)c->ld * sizeof(double), in, (size_t)c->N * sizeof(double),
+                            (size_t)c->N * sizeof(double), (size_t)(e - b), in_kind(mem), c->lane->stream));
+    HIPCHK(hipStreamSynchronize(c->lane->stream));
     return MUSE_OK;
 }
 
 static int ensure_tsample(muse_ctx* c, size_t entries) {
     if (entries <= c->tsample_cap) return MUSE_OK;
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipStreamSynchronize(c->lane->stream));
     if (c->tsample_dev) HIPCHK(hipFree(c->tsample_dev));
     if (c->tsample_pin) HIPCHK(hipHostFree(c->tsample_pin));
     c->tsample_dev = nullptr; c->tsample_pin = nullptr; c->tsample_cap = 0;
@@ -1878,7 +1836,7 @@ static int fd_values_impl(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t
             (void)hipGetLastError();
             c->fid_norm = nullptr;
         }
-        if (c->fid_norm) HIPCHK(launch_normals(seed, (uint64_t)fid_sim, c->ld, c->fid_norm, c->stream));
+        if (c->fid_norm) HIPCHK(launch_normals(seed, (uint64_t)fid_sim, c->ld, c->fid_norm, c->lane->stream));
     }
     // a sampling entry: exp(theta/2) of every block -- a SampleSd, or kBigTheta doubles in the big tier (solver.hpp, begin)
     const int ts_stride = tier_big(c, choose_place(c), 1) ? kBigTheta : kMaxTheta;
@@ -1900,15 +1858,9 @@ static int fd_values_impl(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t
         a.nstd = (int)nfid;
         a.norm_sim0 = s_lo;
         if (fidn && c->fid_norm) {   // the launch is the fiducial problem alone: its normals are in fid_norm (slot 0 of a one-stream cache)
-            a.ncache = c->fid_norm;
-            a.ncache_sim0 = fid_sim;
-            a.ncache_count = 1;
-            a.ncache_mode = 2;
+            attach_ncache(a, c->fid_norm, fid_sim, 1, 2);
         } else if (cached) {
-            a.ncache = c->ncache;
-            a.ncache_sim0 = nc_sim0;
-            a.ncache_count = (int)nc_cnt;
-            a.ncache_mode = held ? 2 : 1;
+            attach_ncache(a, c->ncache, nc_sim0, nc_cnt, held ? 2 : 1);
             if (!held) c->nc_count = 0;   // (overwritten from here on; claimed below once the whole call has ended well)
         }
         a.include_data = 0;
@@ -1949,7 +1901,7 @@ static int fd_values_impl(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t
     }
     if (!ts_in_kernarg)
         HIPCHK(hipMemcpyAsync(c->tsample_dev, c->tsample_pin, (size_t)(per_unit ? n : (int64_t)nt * G) * ts_stride * sizeof(double),
-                              hipMemcpyHostToDevice, c->stream));
+                              hipMemcpyHostToDevice, c->lane->stream));
     {
         BatchArgs& a = a2;
         a.kind = BATCH_FD;
@@ -1962,7 +1914,7 @@ static int fd_values_impl(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t
             a.fid_flag = c->fid_flag;
             a.fid_tag = ++c->fid_tag;
             if (c->fid_tag >= 0x7ffffff0u) {   // (the tag never wraps onto a value the flag may still hold)
-                HIPCHK(hipMemsetAsync(c->fid_flag, 0, 64, c->stream));
+                HIPCHK(hipMemsetAsync(c->fid_flag, 0, 64, c->lane->stream));
                 c->fid_tag = 0;
                 a.fid_tag = ++c->fid_tag;
             }
@@ -1976,12 +1928,7 @@ static int fd_values_impl(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t
         a.tsample = ts_in_kernarg ? nullptr : c->tsample_dev;
         a.scores = c->scores_dev[1];
         a.info = c->info_dev[1];
-        if (cached) {
-            a.ncache = c->ncache;
-            a.ncache_sim0 = nc_sim0;
-            a.ncache_count = (int)nc_cnt;
-            a.ncache_mode = 2;
-        }
+        if (cached) attach_ncache(a, c->ncache, nc_sim0, nc_cnt, 2);
         rc = launch_batch(c, a);
         if (rc) return rc;
     }
@@ -2103,7 +2050,7 @@ static int implicit_impl(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t 
     if (rc) return rc;
     rc = enqueue_results_copy(c, 2, nsims * nt);
     if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipStreamSynchronize(c->lane->stream));
     rc = check_error_flag(c);
     if (rc) return rc;
     for (int64_t e = 0; e < ne; ++e) {

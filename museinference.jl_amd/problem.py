@@ -427,15 +427,8 @@ class HipMuseProblem(AbstractMuseProblem):
                     np.broadcast_to(np.asarray(self.prior.sigma, dtype=np.float64), (self.ntheta,)).copy())
         return None
 
-    def run_muse(self, rng, theta0, *, nsims, maxsteps, theta_rtol, atol, alpha, z0_warm=False, device_loop=None):
-        """The muse! outer loop in the library's native code (muse_run / muse_run_device, include/muse_hip.h): returns
-        (n, theta, hist [n, W], g_sims [n, nsims, nθ], info [n, nsims+1]).  device_loop=True: ONE launch runs every
-        iteration -- map, exchange of the scores between the (all resident) workgroups, step, next map -- and nothing leaves
-        the GPU in between (the default: 42 against 48 us per steady iteration at N = 10^4 x 512 sims, and no host in the loop to be
-        slowed by whatever else the process does); False: one launch per iteration, the algebra on the host.  The same results
-        bit for bit either way; placements other than the resident ones (an element split, N > 10 000) and five to eight theta
-        components with several elements per workgroup run the host loop whatever is asked; so does a context whose loop kernel
-        once failed to keep its workgroups resident (a shared GPU)."""
+    def _run_options(self, nsims, maxsteps, theta_rtol, atol, alpha, z0_warm):
+        """The filled muse_run_options of the native muse! loops (run_muse, run_muse_sharded)."""
         native = self.native_prior()
         if native is None:
             raise _capi.MuseError(-1, "the native muse! loops take a flat or Gaussian prior and ntheta <= MUSE_MAX_THETA "
@@ -446,6 +439,18 @@ class HipMuseProblem(AbstractMuseProblem):
         o.prior_kind, o.z0_warm = int(kind), int(bool(z0_warm))
         for k in range(self.ntheta):
             o.prior_mean[k], o.prior_sigma[k] = float(mean[k]), float(sigma[k])
+        return o
+
+    def run_muse(self, rng, theta0, *, nsims, maxsteps, theta_rtol, atol, alpha, z0_warm=False, device_loop=None):
+        """The muse! outer loop in the library's native code (muse_run / muse_run_device, include/muse_hip.h): returns
+        (n, theta, hist [n, W], g_sims [n, nsims, nθ], info [n, nsims+1]).  device_loop=True: ONE launch runs every
+        iteration -- map, exchange of the scores between the (all resident) workgroups, step, next map -- and nothing leaves
+        the GPU in between (the default: 42 against 48 us per steady iteration at N = 10^4 x 512 sims, and no host in the loop to be
+        slowed by whatever else the process does); False: one launch per iteration, the algebra on the host.  The same results
+        bit for bit either way; placements other than the resident ones (an element split, N > 10 000) and five to eight theta
+        components with several elements per workgroup run the host loop whatever is asked; so does a context whose loop kernel
+        once failed to keep its workgroups resident (a shared GPU)."""
+        o = self._run_options(nsims, maxsteps, theta_rtol, atol, alpha, z0_warm)
         th0 = self._theta(theta0)
         W = _capi.run_hist_width(self.ntheta)
         # (not zero-filled: the library writes every row it reports, the others are cut off below -- at 30 x 513 elements the
@@ -486,16 +491,7 @@ class HipMuseProblem(AbstractMuseProblem):
         [n, count of its elements] (rank 0: the data element first).  With the shared-memory transport and a resident placement
         the loop is ONE persistent launch per rank (scores exchanged through boards in device memory that the ranks map into each
         other by hipIpc, or through one board in pinned host memory); the host-driven loop otherwise -- the same bits."""
-        native = self.native_prior()
-        if native is None:
-            raise _capi.MuseError(-1, "the native muse! loops take a flat or Gaussian prior and ntheta <= MUSE_MAX_THETA "
-                                                     "(muse() runs its loop over the batched maps otherwise)")
-        kind, mean, sigma = native
-        o = _capi.RunOptions()
-        o.nsims, o.maxsteps, o.theta_rtol, o.atol, o.alpha = int(nsims), int(maxsteps), float(theta_rtol), float(atol), float(alpha)
-        o.prior_kind, o.z0_warm = int(kind), int(bool(z0_warm))
-        for k in range(self.ntheta):
-            o.prior_mean[k], o.prior_sigma[k] = float(mean[k]), float(sigma[k])
+        o = self._run_options(nsims, maxsteps, theta_rtol, atol, alpha, z0_warm)
         th0 = self._theta(theta0)
         world, rank = self._nranks, self._rank
         base, extra = divmod(int(nsims), world)

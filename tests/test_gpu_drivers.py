@@ -569,6 +569,43 @@ def test_concurrent_lanes_give_the_same_results(gpu, M, model, N, nth, split):
     ref.close()
 
 
+def test_call_refused_on_a_lane_leaves_lane_0_to_the_next_call(gpu, M):
+    """A map that is refused AFTER its result area's lane was selected ("batch too large": 2 maps x 2^31 elements, found before
+    anything is allocated or launched) must not leave that lane to the calls that follow: synchronize, get_zhat and a warm start
+    work on lane 0 and see ITS resident MAPs, bit-equal to a context with one lane; the maps in flight on the lanes are unharmed."""
+    N, nel = 10000, 40
+    th = np.array([0.4, -0.3])
+    prob = M.HipMuseProblem(None, model="funnel", ntheta=2, N=N)
+    ref = M.HipMuseProblem(None, model="funnel", ntheta=2, N=N)
+    # (area 0's map last: the one-lane context's resident MAPs are then those of lane 0)
+    want = {a: ref.map_and_score_batch(3, 100 * a, 100 * a + nel, th + 0.1 * a, atol=1e-3) for a in (2, 1, 0)}
+    z_want = ref.get_zhat(0, nel)
+
+    def refused(area):
+        with pytest.raises(M.MuseError, match="batch too large"):
+            prob.map_and_score_multi_async(3, 0, 2 ** 31, np.stack([th, th]), result_area=area)
+
+    prob.set_concurrency(3)
+    for a in range(3):
+        prob.map_and_score_batch_async(3, 100 * a, 100 * a + nel, th + 0.1 * a, atol=1e-3, result_area=a)
+    for a in (1, 2):
+        refused(a)
+        prob.synchronize()
+        refused(a)
+        assert np.array_equal(prob.get_zhat(0, nel), z_want), a
+    for a in range(3):
+        g, info = prob.batch_wait(nel, a)
+        assert np.array_equal(g, want[a][0]) and np.array_equal(info, want[a][1]), a
+    refused(2)
+    g, info = prob.map_and_score_batch(3, 0, nel, th, atol=1e-3, z0_mode=M.Z0_WARM)
+    gr, ir = ref.map_and_score_batch(3, 0, nel, th, atol=1e-3, z0_mode=M.Z0_WARM)
+    assert np.all(info["iterations"] == 0) and np.array_equal(g, gr) and np.array_equal(info, ir)
+    refused(1)
+    assert np.array_equal(prob.get_zhat(0, nel), ref.get_zhat(0, nel))
+    prob.close()
+    ref.close()
+
+
 def test_round3_entry_points_edge_cases(gpu, M, O):
     """Empty and degenerate inputs of the round-3 entry points: an empty sim range (with and without the data element), one
     map through the multi-map entry, N = 1 / ntheta = N, a finite-difference grid of one point at offset 0, bad arguments."""
