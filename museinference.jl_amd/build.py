@@ -19,6 +19,8 @@ _API = os.path.join(_HERE, "..", "include", "muse_hip.h")
 _KERNEL_HEADERS = [os.path.join(CSRC, h) for h in ("rng.hpp", "args.hpp", "vec.hpp", "reduce.hpp", "models.hpp", "user_model.hpp", "solver.hpp",
                                                     "step.hpp", "kernels.hpp")]
 _SWITCHES = os.path.join(CSRC, "switches.hpp")
+_HOST_LOOP = os.path.join(CSRC, "host_loop.h")      # host only: the muse! loop muse_run and muse_run_sharded share
+_HANDOFF = os.path.join(CSRC, "comm_handoff.h")     # host only: the RCCL transport's caller -> worker queue
 # source -> (headers it depends on, extra flags)
 # -ffp-contract=off: the sampler's log/sincos sequences and the model gradients are defined in terms
 # of individually rounded IEEE operations (bit-equal to a host evaluation of the same sequence).
@@ -32,15 +34,15 @@ UNITS = {
     **{f"kernels_part{n}": ("kernels_part.hip", _KERNEL_HEADERS + [_API], _DEVICE_FLAGS + [f"-DMUSE_PART={n}"]) for n in range(KERNEL_PARTS)},
     # host code: plain C++ against the HIP runtime API (no device pass)
     # (-ffp-contract=off here too: step.hpp's algebra must round on the host exactly as in the step kernel)
-    "muse_engine": ("muse_engine.cpp", [os.path.join(CSRC, "args.hpp"), os.path.join(CSRC, "step.hpp"), os.path.join(CSRC, "user_model.hpp"), _SWITCHES, _API],
+    "muse_engine": ("muse_engine.cpp", [os.path.join(CSRC, "args.hpp"), os.path.join(CSRC, "step.hpp"), os.path.join(CSRC, "user_model.hpp"), _SWITCHES, _HOST_LOOP, _API],
                         ["-x", "c++", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-O2", "-ffp-contract=off"]),
     # (step.hpp's algebra again: the sharded muse! loop takes the same step as muse_run)
-    "muse_comm": ("muse_comm.cpp", [_API, os.path.join(CSRC, "shm_gather.hpp"), os.path.join(CSRC, "args.hpp"), os.path.join(CSRC, "step.hpp"), _SWITCHES],
+    "muse_comm": ("muse_comm.cpp", [_API, os.path.join(CSRC, "shm_gather.hpp"), os.path.join(CSRC, "args.hpp"), os.path.join(CSRC, "step.hpp"), _SWITCHES, _HOST_LOOP, _HANDOFF],
                       ["-x", "c++", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-O2", "-ffp-contract=off"]),
 }
 COMMON_FLAGS = ["-std=c++17", "-fPIC", "-Wno-unused-value"]
 SOURCES = sorted({os.path.join(CSRC, u[0]) for u in UNITS.values()})
-HEADERS = _KERNEL_HEADERS + [_API, os.path.join(CSRC, "shm_gather.hpp"), _SWITCHES]
+HEADERS = _KERNEL_HEADERS + [_API, os.path.join(CSRC, "shm_gather.hpp"), _SWITCHES, _HOST_LOOP, _HANDOFF]
 
 
 def declared_symbols():

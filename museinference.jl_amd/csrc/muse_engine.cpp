@@ -16,7 +16,7 @@
 
 #include "../../include/muse_hip.h"
 #include "args.hpp"
-#include "step.hpp"
+#include "host_loop.h"
 #include "switches.hpp"
 #include "user_model.hpp"
 
@@ -637,13 +637,14 @@ static void free_run_buffers(muse_ctx* c);
 
 // accessors for muse_comm.cpp (the context layout is private to this file)
 int muse_set_error(int code, const char* msg) { return fail(code, msg ? msg : ""); }
-int muse_ctx_comm_slot(muse_ctx* c, void*** comm, int* device, void** stream) {
+int muse_ctx_comm_slot(muse_ctx* c, void*** comm, int* device, void** stream, int* ntheta) {
     if (!c) return fail(MUSE_ERR_INVALID, "ctx is NULL");
     // the communicator's stream order (RCCL transport: collective stream <- event on the solver's stream) is tied to lane 0:
     // hand out lane 0's stream whatever lane the last map used
     *comm = &c->comm;
     *device = c->device;
     *stream = (void*)c->lanes[0].stream;
+    *ntheta = c->ntheta;
     return MUSE_OK;
 }
 int muse_ctx_switches(muse_ctx* c, const Switches** sw, int* debug) {
@@ -655,12 +656,6 @@ int muse_ctx_switches(muse_ctx* c, const Switches** sw, int* debug) {
 int muse_ctx_set_comm_reserve(muse_ctx* c, int cus) {
     if (!c) return fail(MUSE_ERR_INVALID, "ctx is NULL");
     c->comm_reserve_cus = cus > 0 ? cus : 0;
-    return MUSE_OK;
-}
-int muse_ctx_area_event(muse_ctx* c, int area, void** event, int* ntheta) {
-    if (!c || area < 0 || area >= kResultAreas) return fail(MUSE_ERR_INVALID, "bad result_area");
-    *event = (void*)c->area_done[area];
-    *ntheta = c->ntheta;
     return MUSE_OK;
 }
 int muse_ctx_comm_buffer(muse_ctx* c, size_t doubles, double** buf) {
@@ -1290,80 +1285,24 @@ static int check_run_args(muse_ctx* c, const double* theta0, const muse_run_opti
     if (!c->has_data) return fail(MUSE_ERR_NODATA, "muse_run needs the observed data (muse_set_data)");
     return MUSE_OK;
 }
-static void step_params(const muse_ctx* c, const muse_run_options* o, StepParams& sp) {
-    memset(&sp, 0, sizeof sp);
-    sp.ntheta = c->ntheta;
-    sp.nsims = o->nsims;
-    sp.prior_kind = o->prior_kind;
-    sp.alpha = o->alpha;
-    sp.theta_rtol = o->theta_rtol;
-    for (int k = 0; k < c->ntheta; ++k) {
-        sp.prior_mean[k] = o->prior_mean[k];
-        sp.prior_sigma[k] = o->prior_sigma[k];
-    }
-}
-static int step_error(int err) {
-    switch (err) {
-        case STEP_SINGULAR_LIKE: return fail(MUSE_ERR_INVALID, "muse_run: singular H^-1_like (zero score variance)");
-        case STEP_SINGULAR_POST: return fail(MUSE_ERR_INVALID, "muse_run: singular posterior Hessian");
-        case STEP_DOMAIN:
-            // sqrt of a negative argument is a DomainError in the reference (an H^-1_post' that is not negative definite)
-            return fail(MUSE_ERR_INVALID, "muse_run: DomainError in the convergence test: dtheta' H^-1_post' dtheta > 0 (H^-1_post' is not negative definite)");
-        default: return MUSE_OK;
-    }
-}
-
-// The loop with the algebra on the host: launch, wait, step (step.hpp), launch again.
+// The loop with the algebra on the host (host_loop.h): launch, wait, step (step.hpp), launch again.
 int muse_run(muse_ctx* c, uint64_t seed, const double* theta0, const muse_run_options* o, int32_t* niter_out,
              double* theta_out, double* hist_out, double* gsims_out, muse_info* info_out) {
     int rc = check_ctx(c);
     if (rc) return rc;
     rc = check_run_args(c, theta0, o, niter_out, theta_out, hist_out, gsims_out);
     if (rc) return rc;
-    const int nt = c->ntheta, S = o->nsims;
-    const int64_t H = MUSE_RUN_HIST(nt);
-    StepParams sp;
-    step_params(c, o, sp);
-    StepWork work;
-    double theta[kMaxTheta], theta_next[kMaxTheta], mean[kMaxTheta], var[kMaxTheta];
-    for (int k = 0; k < nt; ++k) theta[k] = theta0[k];
-    std::vector<double> g((size_t)(S + 1) * nt);
-    std::vector<muse_info> info((size_t)S + 1);
-    int n = 0;
-    for (int i = 1; i <= o->maxsteps; ++i) {
-        const double t_start = (double)std::chrono::duration_cast<std::chrono::nanoseconds>(
-                                   std::chrono::steady_clock::now().time_since_epoch()).count() * 1e-9;
-        if (i > 2) {  // convergence on the last two records (src/muse.jl:163-166); a NaN compares false and the loop goes on
-            const int cv = step_converged(nt, hist_out + (int64_t)(i - 2) * H, hist_out + (int64_t)(i - 3) * H, o->theta_rtol);
-            if (cv < 0) return step_error(STEP_DOMAIN);
-            if (cv > 0) break;
-        }
-        const int z0_mode = (i > 1 || o->z0_warm) ? MUSE_Z0_WARM : MUSE_Z0_ZERO;
+    const int S = o->nsims;
+    auto run_map = [&](int i, const double* theta, int z0_mode, double* g, muse_info* info) {
         // every iteration re-draws the same streams at a new theta (src/muse.jl:134,169): the first one stores the
         // standard normals, the later ones load them instead of running the generator again
         MapOpts mo;
         mo.ncache_mode = (i == 1 && !ncache_holds(c, seed, 0, S)) ? 1 : 2;
         mo.lanes_ok = false;
-        rc = map_async_impl(c, seed, 0, S, 1, theta, o->atol, z0_mode, 0, mo);
-        if (rc) return rc;
-        rc = muse_batch_wait(c, 0, g.data(), info.data());
-        if (rc) return rc;
-        double* h = hist_out + (int64_t)(i - 1) * H;
-        double* gs = gsims_out + (int64_t)(i - 1) * S * nt;
-        memcpy(gs, g.data() + nt, (size_t)S * nt * sizeof(double));
-        if (info_out) memcpy(info_out + (int64_t)(i - 1) * (S + 1), info.data(), ((size_t)S + 1) * sizeof(muse_info));
-        for (int k = 0; k < nt; ++k) step_moments(k, nt, S, gs, mean[k], var[k]);
-        const int err = step_record(sp, theta, g.data(), mean, var, h, theta_next, work);
-        if (err != STEP_OK) return step_error(err);
-        for (int k = 0; k < nt; ++k) theta[k] = theta_next[k];
-        const double t_end = (double)std::chrono::duration_cast<std::chrono::nanoseconds>(
-                                 std::chrono::steady_clock::now().time_since_epoch()).count() * 1e-9;
-        h[7 * nt + nt * nt] = t_end - t_start;
-        n = i;
-    }
-    *niter_out = n;
-    for (int k = 0; k < nt; ++k) theta_out[k] = theta[k];
-    return MUSE_OK;
+        const int e = map_async_impl(c, seed, 0, S, 1, theta, o->atol, z0_mode, 0, mo);
+        return e ? e : muse_batch_wait(c, 0, g, info);
+    };
+    return host_muse_loop("muse_run", c->ntheta, theta0, o, (int64_t)S + 1, run_map, niter_out, theta_out, hist_out, gsims_out, info_out);
 }
 
 // The same loop with NO host in it: ONE launch of the loop kernel (muse_kernels.hip, muse_loop_kernel) runs every
@@ -1618,7 +1557,7 @@ static int run_loop_launch(muse_ctx* c, uint64_t seed, const double* theta0, con
     a.scratch = c->lane->scratch;
     LoopArgs l;
     memset(&l, 0, sizeof l);
-    step_params(c, o, l.sp);
+    step_params(c->ntheta, o, l.sp);
     l.maxsteps = maxsteps;
     l.z0_warm = o->z0_warm ? 1 : 0;
     l.hist_out = r.hist;

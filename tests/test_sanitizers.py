@@ -1,9 +1,10 @@
 """Sanitizer builds of everything that runs without a GPU: the shared-memory transport's lock-free protocol
 (museinference.jl_amd/csrc/shm_gather.hpp) under ThreadSanitizer -- with the ranks as THREADS sharing one mapping, the form
 the sanitizer can follow -- and under AddressSanitizer + UndefinedBehaviorSanitizer with the ranks as processes; the CPU
-oracle (oracle/muse_oracle.c) under ASan + UBSan on awkward shapes.  CPU only, never on the GPU box's device (GPU
-AddressSanitizer is not available on this pool).  Not covered: muse_comm.cpp's RCCL worker thread, which cannot run
-without a device; its hand-off is a mutex-protected queue plus one atomic flag per result area."""
+oracle (oracle/muse_oracle.c) under ASan + UBSan on awkward shapes; the hand-off between the RCCL transport's caller and
+its worker thread (csrc/comm_handoff.h) under ThreadSanitizer; the host-driven muse! loop (csrc/host_loop.h) with a
+synthetic map under ASan + UBSan.  CPU only, never on the GPU box's device (GPU AddressSanitizer is not available on this
+pool)."""
 import os
 import subprocess
 import uuid
@@ -64,6 +65,27 @@ def test_step_algebra_under_address_and_ub_sanitizer(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, env=ENV, timeout=600)
     _clean(r, "step.hpp under ASan/UBSan")
     assert "step driver ok" in r.stdout
+
+
+def test_host_loop_under_address_and_ub_sanitizer(tmp_path):
+    """csrc/host_loop.h (the loop of muse_run and of muse_run_sharded's host loop) around a synthetic map: z0 modes, where it
+    stops, every record against step_moments + step_record bit for bit, map errors passed through, "singular"."""
+    exe = _build(tmp_path, "host_loop_asan", ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                                              "-ffp-contract=off", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__",
+                                              os.path.join(HERE, "native", "host_loop_driver.cpp")])
+    r = subprocess.run([exe], capture_output=True, text=True, env=ENV, timeout=600)
+    _clean(r, "host_loop.h under ASan/UBSan")
+    assert "host loop driver ok" in r.stdout
+
+
+def test_rccl_handoff_under_thread_sanitizer(tmp_path):
+    """csrc/comm_handoff.h: producer and consumer as muse_comm.cpp's start / wait and worker use it, then stop with and without
+    a pending entry."""
+    exe = _build(tmp_path, "handoff_tsan", ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=thread", os.path.join(HERE, "native", "handoff_driver.cpp"),
+                                            "-lpthread"])
+    r = subprocess.run([exe, "6000"], capture_output=True, text=True, env=ENV, timeout=600)
+    _clean(r, "TSan, hand-off of the result areas")
+    assert "handoff driver ok: 6000 rounds" in r.stdout
 
 
 def test_oracle_under_address_and_ub_sanitizer(tmp_path):
