@@ -145,8 +145,13 @@ int muse_set_constants(muse_ctx* ctx, int k, const double* values, int64_t count
  * constants are the context's; a model without them needs no context (ctx may be NULL, and no GPU is touched).  Built-in models:
  * MUSE_ERR_INVALID. */
 int muse_model_eval(muse_ctx* ctx, double iv, double sd, double x, double z, double n1, double n2, int64_t i, double* out);
-/* 1 when the library's model supplies second derivatives (the built-in models; a user header with MUSE_MODEL_SECOND), i.e.
- * when muse_implicit_H_* accept it; 0 otherwise. */
+/* The second derivatives of a header of the two-parameter family that states them (MUSE_MODEL_PAIR_SECOND, include/muse_model.h),
+ * on the host for one element of a block with parameters a, b: out[8] = { ozz, ozx, gza, gzb, sxa, sxb of muse_model_pair_second
+ * at (x, z), xa, xb of muse_model_pair_dx at (n1, n2) }, the coefficients from muse_model_coefs(a, b).  ctx as for
+ * muse_model_eval (NULL when the model has no run-time constants).  Every other library: MUSE_ERR_INVALID. */
+int muse_model_eval_pair_second(muse_ctx* ctx, double a, double b, double x, double z, double n1, double n2, int64_t i, double* out);
+/* 1 when the library's model supplies second derivatives (the built-in models; a user header with MUSE_MODEL_SECOND or, in the
+ * two-parameter family, MUSE_MODEL_PAIR_SECOND), i.e. when muse_implicit_H_* accept it; 0 otherwise. */
 int muse_model_has_second(void);
 /* The normals cache of plain maps.  A simulation's stream depends only on (seed, simulation index) (split_rng,
  * src/util.jl:87-92), and the reference's loops draw the same streams again and again -- every iteration of muse!
@@ -327,7 +332,8 @@ int muse_fd_values_columns(muse_ctx* ctx, uint64_t seed, int64_t sim_begin, int6
  *   gradients (IterativeSolvers.cg defaults: x0 = 0, reltol sqrt(eps), maxiter = cg_maxiter, reference 100);
  *   zhat from zero(z) to `atol` (the reference hard-codes 1e-1 here, src/muse.jl:344).  The reference takes the
  *   derivative operands by nested AD; for the compiled-in models they are closed forms, for a user-supplied model the
- *   header's muse_model_second / muse_model_dx_dsd (include/muse_model.h; a header without them is refused).
+ *   header's muse_model_second / muse_model_dx_dsd -- in the two-parameter family muse_model_pair_second / muse_model_pair_dx --
+ *   (include/muse_model.h; a header without them is refused).
  * Hs_out [nsims][ntheta][ntheta] host; cg_iters_out [nsims][ntheta] host (may be NULL; the
  * metadata[:implicit_diff_cg_hists] of src/muse.jl:405). */
 int muse_implicit_H_batch(muse_ctx* ctx, uint64_t seed, int64_t sim_begin, int64_t sim_end, const double* theta0,
@@ -336,6 +342,18 @@ int muse_implicit_H_batch(muse_ctx* ctx, uint64_t seed, int64_t sim_begin, int64
  * cg_iters_out [n] (may be NULL). */
 int muse_implicit_H_columns(muse_ctx* ctx, uint64_t seed, int64_t sim_begin, int64_t col_begin, int64_t col_end,
                             const double* theta0, double atol, int cg_maxiter, double* cols_out, int32_t* cg_iters_out);
+/* The same two entries with the remaining keywords of the reference's branch: conjugate gradients stop at
+ * |r| <= max(cg_reltol |b|, cg_abstol) or after cg_maxiter iterations (implicit_diff_cg_kwargs, splatted into IterativeSolvers.cg:
+ * src/muse.jl:381; cg_maxiter = 0 leaves H = H1), and bit MUSE_IMPLICIT_H1_IS_ZERO of `flags` is implicit_diff_H1_is_zero
+ * (src/muse.jl:353: the H1 sums are skipped, H1 = 0).  muse_implicit_H_batch / _columns ARE these entries with cg_reltol = sqrt(eps),
+ * cg_abstol = 0, flags = 0 -- the same bits.  Values other than those are honoured by the kernels of the two-parameter family
+ * (MUSE_MODEL_PAIR_SECOND); every other library refuses them with MUSE_ERR_INVALID: its kernels run the defaults. */
+#define MUSE_IMPLICIT_H1_IS_ZERO 1
+int muse_implicit_H_batch_ex(muse_ctx* ctx, uint64_t seed, int64_t sim_begin, int64_t sim_end, const double* theta0, double atol,
+                             int cg_maxiter, double cg_reltol, double cg_abstol, int flags, double* Hs_out, int32_t* cg_iters_out);
+int muse_implicit_H_columns_ex(muse_ctx* ctx, uint64_t seed, int64_t sim_begin, int64_t col_begin, int64_t col_end,
+                               const double* theta0, double atol, int cg_maxiter, double cg_reltol, double cg_abstol, int flags,
+                               double* cols_out, int32_t* cg_iters_out);
 
 /* ---- multi-GPU exchange of the per-sim accumulators -------------------------------------------- */
 /* Collectives C1-C3 of SURVEY.md §2: gather of per-rank score blocks (so that every rank reduces

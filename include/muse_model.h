@@ -107,7 +107,29 @@
  * Everything of the C ABI applies -- batched maps in every placement (register/LDS resident, streaming, workgroup clusters, an
  * element split), multi-map launches, lanes, the native muse! loops (muse_run, muse_run_device: the step between two iterations
  * calls muse_model_coefs on the device -- the same statements as on the host, the same bits --, muse_run_sharded), both exchanges
- * between ranks, the finite-difference get_H! -- except the implicit-differentiation get_H! and more than MUSE_MAX_THETA parameters.
+ * between ranks, the finite-difference get_H! -- except more than MUSE_MAX_THETA parameters, and the implicit-differentiation get_H!
+ * for a header that states its second derivatives:
+ *
+ * SECOND DERIVATIVES OF THE TWO-PARAMETER FAMILY (optional).  A header that says
+ *     #define MUSE_MODEL_PAIR_SECOND 1                 (names of their own: MUSE_MODEL_SECOND / muse_model_second are the one-parameter
+ *                                                       family's, with another signature)
+ * also defines, with g = d(1/2 o)/dz the gradient, sa = -1/2 do/da and sb = -1/2 do/db the element's full score terms -- derivatives
+ * in a and b taken THROUGH the coefficients and written in the coefficients, as the score is --,
+ *     MUSE_MODEL_FN void muse_model_pair_second(const double* c, double x, double z, double* ozz, double* ozx, double* gza, double* gzb,
+ *                                               double* sxa, double* sxb, long i);
+ *         *ozz = dg/dz, *ozx = dg/dx, *gza = dg/da, *gzb = dg/db, *sxa = d sa / dx, *sxb = d sb / dx
+ *     MUSE_MODEL_FN void muse_model_pair_dx(const double* c, double n1, double n2, double* xa, double* xb, long i);
+ *         dx/da, dx/db of muse_model_sample at fixed normals (reads c[0], c[1] only, like the draw)
+ * both finite for c = {0, 0, 0, 0} at x = z = 0 and for i >= N (checked when a context is created).  The engine forms, elementwise at
+ * (x, zhat, theta0), for column j of H -- block j mod K, parameter q = a for j < K and b otherwise --
+ *     Hessian_z logLike w = -ozz_i w_i,     d/dp grad_z logLike = -gzp_i,     d/dq grad_z logLike(x(theta), zhat, theta0) = -ozx_i xq_i,
+ *     H1[p][j] = sum_{i in the column's block} sxp_i xq_i   for p that block's two parameters, 0 for every other p
+ * (src/muse.jl:353-379), and muse_implicit_H_* accept the library (muse_model_has_second() = 1).  models/offset_noise.h is the shipped
+ * member: z_i ~ N(0, 1), x_i ~ N(z_i + mu_k, e^tau_k); ozz = 1 + iv, ozx = -iv, gza = sxa = iv, gzb = sxb = iv (x - z - mu), xa = 1,
+ * xb = 1/2 sd n2.  (For normal_mean_var's terms: ozz = 1 + iv, ozx = -1, gza = -iv, gzb = -iv (z - mu), sxa = sxb = 0, xa = 1,
+ * xb = 1/2 sd n1; models/normal_mean_var.h itself states none and runs get_H! by finite differences.)
+ * museinference_jl_amd.ElementwiseModel.from_pair_expressions writes both functions from the model's terms; muse_model_eval_pair_second
+ * of muse_hip.h evaluates them on the host, which is what check_model_consistency differentiates numerically.
  */
 #ifndef MUSE_MODEL_H
 #define MUSE_MODEL_H

@@ -275,6 +275,36 @@ function implicit_H_columns(prob::HipMuseProblem, seed::Integer, sim_begin, col_
                 prob.ctx, UInt64(seed), sim_begin, col_begin, col_end, standardizeθ(prob, θ₀), atol, cg_maxiter, cols, its))
     cols, its
 end
+# The same two with the remaining keywords of the reference's branch (cg_reltol, cg_abstol: IterativeSolvers.cg's keywords; H1_is_zero: get_H!'s implicit_diff_H1_is_zero -- values other than the
+#  defaults are honoured for headers of the two-parameter family and refused for every other model)
+function implicit_H_batch_ex(prob::HipMuseProblem, seed::Integer, sims::UnitRange, θ₀; atol=1e-1, cg_maxiter=100, cg_reltol=sqrt(eps()),
+                          cg_abstol=0.0, H1_is_zero=false)
+    n = length(sims)
+    Hs = Array{Float64}(undef, prob.nθ, prob.nθ, n); its = Matrix{Int32}(undef, prob.nθ, n)
+    check(ccall((:muse_implicit_H_batch_ex, libmuse_hip), Cint,
+                (Ptr{Cvoid}, UInt64, Int64, Int64, Ptr{Float64}, Float64, Cint, Float64, Float64, Cint, Ptr{Float64}, Ptr{Int32}),
+                prob.ctx, UInt64(seed), first(sims), last(sims) + 1, standardizeθ(prob, θ₀), atol, cg_maxiter, cg_reltol, cg_abstol,
+                H1_is_zero ? 1 : 0, Hs, its))
+    [permutedims(Hs[:, :, s]) for s in 1:n], its          # (the C ABI is row-major [sim][i][j])
+end
+function implicit_H_columns_ex(prob::HipMuseProblem, seed::Integer, sim_begin, col_begin, col_end, θ₀; atol=1e-1, cg_maxiter=100,
+                            cg_reltol=sqrt(eps()), cg_abstol=0.0, H1_is_zero=false)
+    cols = Matrix{Float64}(undef, prob.nθ, col_end - col_begin); its = Vector{Int32}(undef, col_end - col_begin)
+    check(ccall((:muse_implicit_H_columns_ex, libmuse_hip), Cint,
+                (Ptr{Cvoid}, UInt64, Int64, Int64, Int64, Ptr{Float64}, Float64, Cint, Float64, Float64, Cint, Ptr{Float64}, Ptr{Int32}),
+                prob.ctx, UInt64(seed), sim_begin, col_begin, col_end, standardizeθ(prob, θ₀), atol, cg_maxiter, cg_reltol, cg_abstol,
+                H1_is_zero ? 1 : 0, cols, its))
+    cols, its
+end
+# The second derivatives of a header of the two-parameter family (MUSE_MODEL_PAIR_SECOND) for one element on the host:
+# (ozz, ozx, gza, gzb, sxa, sxb, xa, xb)
+function model_eval_pair_second(prob::HipMuseProblem, a, b, x, z, n1, n2, i::Integer)
+    out = Vector{Float64}(undef, 8)
+    check(ccall((:muse_model_eval_pair_second, libmuse_hip), Cint,
+                (Ptr{Cvoid}, Float64, Float64, Float64, Float64, Float64, Float64, Int64, Ptr{Float64}),
+                prob.ctx, a, b, x, z, n1, n2, i, out))
+    out
+end
 
 # One process per GPU (e.g. MPI.jl ranks or Distributed workers pinned to devices): after
 #   id = rank == 0 ? comm_unique_id() : nothing;  id = bcast(id);  comm_init(prob, nranks, rank, id)

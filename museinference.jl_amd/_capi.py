@@ -14,6 +14,7 @@ MODEL_FUNNEL, MODEL_NOISE, MODEL_SMOOTH, MODEL_USER = 0, 1, 2, 3
 MODELS = {"funnel": MODEL_FUNNEL, "noise": MODEL_NOISE, "smooth": MODEL_SMOOTH}   # the built-in models of libmuse_hip.so
 MEM_HOST, MEM_DEVICE = 0, 1
 Z0_ZERO, Z0_TRUE, Z0_WARM = 0, 1, 2
+IMPLICIT_H1_IS_ZERO = 1   # muse_implicit_H_*_ex, flags (MUSE_IMPLICIT_H1_IS_ZERO)
 MAX_THETA = 8
 MAX_MAPS = 8
 UNIQUE_ID_BYTES = 128
@@ -79,6 +80,7 @@ SIGNATURES = {
     "muse_set_normals_cache": (_i, [_vp, _i]),
     "muse_set_constants": (_i, [_vp, _i, _vp, _i64, _i]),
     "muse_model_eval": (_i, [_vp, _d, _d, _d, _d, _d, _d, _i64, _vp]),
+    "muse_model_eval_pair_second": (_i, [_vp, _d, _d, _d, _d, _d, _d, _i64, _vp]),
     "muse_model_has_second": (_i, []),
     "muse_run_sharded": (_i, [_vp, _u64, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp]),
     "muse_get_zhat": (_i, [_vp, _i64, _i64, _vp, _i]),
@@ -87,6 +89,8 @@ SIGNATURES = {
     "muse_implicit_H_batch": (_i, [_vp, _u64, _i64, _i64, _vp, _d, _i, _vp, _vp]),
     "muse_fd_jacobian_columns": (_i, [_vp, _u64, _i64, _i64, _i64, _vp, _vp, _d, _i, _i64, _vp, _vp]),
     "muse_implicit_H_columns": (_i, [_vp, _u64, _i64, _i64, _i64, _vp, _d, _i, _vp, _vp]),
+    "muse_implicit_H_batch_ex": (_i, [_vp, _u64, _i64, _i64, _vp, _d, _i, _d, _d, _i, _vp, _vp]),
+    "muse_implicit_H_columns_ex": (_i, [_vp, _u64, _i64, _i64, _i64, _vp, _d, _i, _d, _d, _i, _vp, _vp]),
     "muse_fd_values_columns": (_i, [_vp, _u64, _i64, _i64, _i64, _vp, _i, _vp, _i, _d, _i, _i64, _vp, _vp]),
     "muse_comm_unique_id": (_i, [_vp]),
     "muse_comm_unique_id_ex": (_i, [_i, C.c_int64, _vp]),

@@ -91,7 +91,8 @@ struct BatchArgs {
     int ntheta, kind;
     int64_t bnd[kMaxTheta + 1];  // block k = elements [bnd[k], bnd[k+1])
     int bnd32[kMaxTheta + 1];    // the same, 32-bit (N < 2^28), for the per-element block lookup
-    int pad0_;
+    int imp_flags;    // BATCH_IMPLICIT: bit 0 = H1 is zero (src/muse.jl:353): its sums are skipped.  Read by the kernels of the
+                      // two-parameter family only (the other implicit kernels run IterativeSolvers.cg's defaults; was padding)
     uint64_t seed;
     double atol;
     int nproblems, include_data, z0_mode, store_zhat;
@@ -149,9 +150,12 @@ struct BatchArgs {
     // fid_tag before it loads its warm start (the fiducial's workgroup releases its stores and sets the flag: solver.hpp, run)
     int fd_fold;
     unsigned int fid_tag;
-    int64_t fid_sim;
+    union {
+        int64_t fid_sim;           // BATCH_FD
+        double cg_abstol;          // BATCH_IMPLICIT (two-parameter family): CG stops at |r| <= max(cg_reltol |b|, cg_abstol)
+    };
     unsigned int* fid_flag;
-    int64_t pad3_;
+    double cg_reltol;              // BATCH_IMPLICIT (two-parameter family; was padding)
     union {  // read from the kernarg segment only (never copied to LDS)
         alignas(16) MapTheta maps[kMaxMaps];  // theta of every map, nmaps > 1
         BigTheta big;                         // ntheta > kMaxTheta

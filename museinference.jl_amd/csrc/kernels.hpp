@@ -117,7 +117,8 @@ map_score_kernel(const BatchArgs /*read via the kernarg segment*/) {
             sv.parity = 0;
             wg_barrier<!Model::kStencil>();
             load_problem_theta<!Model::kStencil>(a, args_lds, p, tid);
-            if constexpr (IMPLICIT) sv.run_implicit(p, cl_scratch, lds_x, lds_g);
+            if constexpr (IMPLICIT && Model::kPair) sv.run_implicit_pair(p, cl_scratch, lds_x, lds_g);
+            else if constexpr (IMPLICIT) sv.run_implicit(p, cl_scratch, lds_x, lds_g);
             else sv.run(p, cl_scratch, lds_x, lds_g);
         }
 #ifdef MUSE_STAMPS
@@ -153,7 +154,8 @@ map_score_kernel(const BatchArgs /*read via the kernarg segment*/) {
                 Solver<Model, Place> sv(a, tid, red, shs);
                 sv.pk[0] = pk0;
                 sv.pk[1] = pk1;
-                if constexpr (IMPLICIT) sv.run_implicit(p, wg_scratch, lds_x, lds_g);
+                if constexpr (IMPLICIT && Model::kPair) sv.run_implicit_pair(p, wg_scratch, lds_x, lds_g);
+                else if constexpr (IMPLICIT) sv.run_implicit(p, wg_scratch, lds_x, lds_g);
                 else sv.run(p, wg_scratch, lds_x, lds_g);
             }
             // (raw barriers for the elementwise models: the MAP's stores keep draining while the next problem starts)
@@ -934,10 +936,18 @@ hipError_t loop_place(const LaunchShape& s, const LoopCall& c) {
     X template hipError_t loop_place<M>(const LaunchShape&, const LoopCall&);
 #define MUSE_INSTANTIATE_USER_BIG(X, M) X template hipError_t launch_place_big<M>(const LaunchShape&, const BatchArgs&, hipStream_t);
 #endif
-#ifdef MUSE_MODEL_PAIR   // two parameters per block: tiers of 2, 4 and 8 components (1, 2, up to 4 blocks); no implicit differentiation, no big tier
+#ifdef MUSE_MODEL_PAIR   // two parameters per block: tiers of 2, 4 and 8 components (1, 2, up to 4 blocks); no big tier; the implicit
+                         // differentiation's kernels for a header that states its second derivatives (MUSE_MODEL_PAIR_SECOND) only
+#ifdef MUSE_MODEL_PAIR_SECOND
+#define MUSE_INSTANTIATE_PAIR(X, M)                                                                 \
+    X template hipError_t launch_place<M>(const LaunchShape&, const BatchArgs&, hipStream_t);       \
+    X template hipError_t launch_place_implicit<M>(const LaunchShape&, const BatchArgs&, hipStream_t); \
+    X template hipError_t loop_place<M>(const LaunchShape&, const LoopCall&);
+#else
 #define MUSE_INSTANTIATE_PAIR(X, M)                                                                 \
     X template hipError_t launch_place<M>(const LaunchShape&, const BatchArgs&, hipStream_t);       \
     X template hipError_t loop_place<M>(const LaunchShape&, const LoopCall&);
+#endif
 #define MUSE_PART_0(X) MUSE_INSTANTIATE_PAIR(X, UserModel<2>)
 #define MUSE_PART_1(X) MUSE_INSTANTIATE_PAIR(X, UserModel<4>)
 #define MUSE_PART_2(X) MUSE_INSTANTIATE_PAIR(X, UserModel<kMaxTheta>)

@@ -143,6 +143,25 @@ struct UserModel {
     __device__ static __forceinline__ void score(const double* c, double s0, double s1, double n, double& ga, double& gb) {
         muse_model_score(c, s0, s1, n, &ga, &gb);
     }
+#ifdef MUSE_MODEL_PAIR_SECOND  // (include/muse_model.h: the operands of the implicit-differentiation get_H!, Solver::run_implicit)
+    // q[0..5] = {ozz, ozx, gza, gzb, sxa, sxb}; the pad element and the phantom slots: all zero (no contribution, a zero Hessian
+    // entry that only ever multiplies a zero direction)
+    __device__ static __forceinline__ void second(const PairGv& c, double x, double z, double* q, int i) {
+        muse_model_pair_second(c.c, x, z, &q[0], &q[1], &q[2], &q[3], &q[4], &q[5], (long)i);
+    }
+    __device__ static __forceinline__ void second(const PairGp& c, double x, double z, double* q, int i) {
+        muse_model_pair_second(c.p, x, z, &q[0], &q[1], &q[2], &q[3], &q[4], &q[5], (long)i);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) q[k] = c.valid ? q[k] : 0.0;
+    }
+    // dx_i / da_k, dx_i / db_k at fixed normals, from the block's coefficients at the theta of the draw
+    __device__ static __forceinline__ void dx(const PairGv& c, double n1, double n2, double& xa, double& xb, int i) {
+        muse_model_pair_dx(c.c, n1, n2, &xa, &xb, (long)i);
+    }
+    __device__ static __forceinline__ void dx(const PairGp& c, double n1, double n2, double& xa, double& xb, int i) {
+        muse_model_pair_dx(c.p, n1, n2, &xa, &xb, (long)i);
+    }
+#endif
 };
 #endif
 #endif

@@ -571,6 +571,15 @@ int muse_ctx_create(int model, int64_t N, int ntheta, int device, muse_ctx** out
         if (!(g0 == 0.0 && acc == 1.25 && t0 == 0.0 && t1 == 0.0))
             return fail(MUSE_ERR_INVALID, "model " MUSE_MODEL_NAME ": with all four coefficients 0 and x = z = 0, muse_model_grad must return 0 and "
                                           "leave acc unchanged and muse_model_score_terms must give 0, 0 (include/muse_model.h)");
+#ifdef MUSE_MODEL_PAIR_SECOND
+        double q[8];
+        muse_model_pair_second(zero4, 0.0, 0.0, &q[0], &q[1], &q[2], &q[3], &q[4], &q[5], (long)N);
+        muse_model_pair_dx(zero4, 0.0, 0.0, &q[6], &q[7], (long)N);
+        for (int k = 0; k < 8; ++k)
+            if (!isfinite(q[k]))
+                return fail(MUSE_ERR_INVALID, "model " MUSE_MODEL_NAME ": muse_model_pair_second and muse_model_pair_dx must be finite with all four "
+                                              "coefficients 0 at x = z = 0 (include/muse_model.h)");
+#endif
     }
 #else
     {   // the zero-element requirements of include/muse_model.h (the pad element of an odd-length vector must not contribute)
@@ -827,7 +836,13 @@ int muse_set_constants(muse_ctx* c, int k, const double* values, int64_t count, 
 #endif
 }
 int muse_model_has_second(void) {
-#if defined(MUSE_USER_MODEL_HEADER) && (!defined(MUSE_MODEL_SECOND) || defined(MUSE_MODEL_PAIR))
+#if defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_PAIR)
+#ifdef MUSE_MODEL_PAIR_SECOND
+    return 1;
+#else
+    return 0;
+#endif
+#elif defined(MUSE_USER_MODEL_HEADER) && !defined(MUSE_MODEL_SECOND)
     return 0;
 #else
     return 1;
@@ -873,6 +888,27 @@ int muse_model_eval(muse_ctx* c, double iv, double sd, double x, double z, doubl
 #else
     (void)c; (void)iv; (void)sd; (void)x; (void)z; (void)n1; (void)n2; (void)i; (void)out;
     return fail(MUSE_ERR_INVALID, "muse_model_eval evaluates a user-supplied model's header; this library holds the built-in models");
+#endif
+}
+int muse_model_eval_pair_second(muse_ctx* c, double a, double b, double x, double z, double n1, double n2, int64_t i, double* out) {
+#if defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_PAIR_SECOND)
+#ifdef MUSE_MODEL_NCONST
+    int rc = check_ctx(c);   // (the model's run-time constants become this context's)
+    if (rc) return rc;
+#else
+    (void)c;                 // a model without run-time constants needs no context (and no GPU) for this
+#endif
+    if (!out || i < 0) return fail(MUSE_ERR_INVALID, "bad argument");
+    double cf[4] = {0.0, 0.0, 0.0, 0.0};
+    (void)muse_model_coefs(a, b, cf);
+    // out = {ozz, ozx, gza, gzb, sxa, sxb, xa, xb}
+    muse_model_pair_second(cf, x, z, &out[0], &out[1], &out[2], &out[3], &out[4], &out[5], (long)i);
+    muse_model_pair_dx(cf, n1, n2, &out[6], &out[7], (long)i);
+    return MUSE_OK;
+#else
+    (void)c; (void)a; (void)b; (void)x; (void)z; (void)n1; (void)n2; (void)i; (void)out;
+    return fail(MUSE_ERR_INVALID, "muse_model_eval_pair_second evaluates the second derivatives of a header of the two-parameter family "
+                                  "(MUSE_MODEL_PAIR_SECOND, include/muse_model.h); this library's model states none");
 #endif
 }
 int muse_set_normals_cache(muse_ctx* c, int enabled) {
@@ -1955,13 +1991,30 @@ int muse_fd_jacobian_batch(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_
 
 // Columns [e_begin, e_end) of the same list for the implicit-differentiation H; per_column: one element per column
 // (each repeats the simulation's sample and its atol MAP), else one element per simulation (whole simulations only).
+struct CgOptions {   // IterativeSolvers.cg's keywords and get_H!'s implicit_diff_H1_is_zero (muse_implicit_H_*_ex)
+    int maxiter;
+    double reltol, abstol;
+    int flags;
+};
+static const double kCgReltolDefault = 1.4901161193847656e-08;   // sqrt(eps): what the kernels of the other models compute themselves
 static int implicit_impl(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t e_begin, int64_t e_end, bool per_column,
-                         const double* theta0, double atol, int cg_maxiter, double* cols_out, int32_t* cg_iters_out) {
+                         const double* theta0, double atol, const CgOptions& cg, double* cols_out, int32_t* cg_iters_out) {
     const int nt = c->ntheta;
     const int64_t ne = e_end - e_begin;
     if (!muse_model_has_second())
         return fail(MUSE_ERR_INVALID, "the implicit-differentiation H needs second derivatives, which this model's header does not "
-                                      "supply (MUSE_MODEL_SECOND, include/muse_model.h): use the finite-difference entries");
+                                      "supply (MUSE_MODEL_SECOND or MUSE_MODEL_PAIR_SECOND, include/muse_model.h): use the finite-difference entries");
+    if (!(cg.reltol >= 0.0) || !(cg.abstol >= 0.0) || !isfinite(cg.reltol) || !isfinite(cg.abstol))
+        return fail(MUSE_ERR_INVALID, "cg_reltol and cg_abstol must be finite and >= 0");
+    if (cg.flags & ~MUSE_IMPLICIT_H1_IS_ZERO) return fail(MUSE_ERR_INVALID, "unknown bits in flags");
+#if !(defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_PAIR_SECOND))
+    // The implicit kernels of the built-in models and of the one-parameter family run IterativeSolvers.cg's defaults and always form
+    // H1: anything else is refused, never ignored.
+    if (cg.maxiter < 1 || cg.reltol != kCgReltolDefault || cg.abstol != 0.0 || cg.flags != 0)
+        return fail(MUSE_ERR_INVALID, "this model's implicit-differentiation kernels run conjugate gradients with cg_reltol = sqrt(eps), "
+                                      "cg_abstol = 0, cg_maxiter >= 1 and form H1: other values are honoured for headers of the "
+                                      "two-parameter family only (MUSE_MODEL_PAIR_SECOND, include/muse_model.h)");
+#endif
     if (ne == 0) return MUSE_OK;
     if (ne > 0x7fffffff) return fail(MUSE_ERR_INVALID, "batch too large");
     const int64_t s_lo = sim_begin + e_begin / nt, s_hi = sim_begin + (e_end - 1) / nt + 1;
@@ -1977,7 +2030,10 @@ static int implicit_impl(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t 
     a.kind = BATCH_IMPLICIT;
     a.seed = seed;
     a.atol = atol;
-    a.cg_maxiter = cg_maxiter;
+    a.cg_maxiter = cg.maxiter;
+    a.cg_reltol = cg.reltol;
+    a.cg_abstol = cg.abstol;
+    a.imp_flags = cg.flags;
     a.imp_split = per_column ? nt : 1;
     a.p0 = per_column ? (int)(e_begin - (s_lo - sim_begin) * nt) : 0;
     a.nproblems = (int)(per_column ? ne : nsims);
@@ -2002,23 +2058,34 @@ static int implicit_impl(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t 
     return MUSE_OK;
 }
 
-int muse_implicit_H_columns(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t col_begin, int64_t col_end,
-                            const double* theta0, double atol, int cg_maxiter, double* cols_out, int32_t* cg_iters_out) {
+int muse_implicit_H_columns_ex(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t col_begin, int64_t col_end, const double* theta0,
+                               double atol, int cg_maxiter, double cg_reltol, double cg_abstol, int flags, double* cols_out,
+                               int32_t* cg_iters_out) {
     int rc = check_ctx(c);
     if (rc) return rc;
     if (!theta0 || !cols_out) return fail(MUSE_ERR_INVALID, "NULL argument");
     if (col_end < col_begin || col_begin < 0 || sim_begin < 0) return fail(MUSE_ERR_INVALID, "bad column range");
-    if (cg_maxiter < 1) return fail(MUSE_ERR_INVALID, "cg_maxiter must be >= 1");
-    return implicit_impl(c, seed, sim_begin, col_begin, col_end, true, theta0, atol, cg_maxiter, cols_out, cg_iters_out);
+    if (cg_maxiter < 0) return fail(MUSE_ERR_INVALID, "cg_maxiter must be >= 0");
+    const CgOptions cg = {cg_maxiter, cg_reltol, cg_abstol, flags};
+    return implicit_impl(c, seed, sim_begin, col_begin, col_end, true, theta0, atol, cg, cols_out, cg_iters_out);
 }
 
-int muse_implicit_H_batch(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t sim_end, const double* theta0, double atol,
-                          int cg_maxiter, double* Hs_out, int32_t* cg_iters_out) {
+int muse_implicit_H_columns(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t col_begin, int64_t col_end,
+                            const double* theta0, double atol, int cg_maxiter, double* cols_out, int32_t* cg_iters_out) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (cg_maxiter < 1) return fail(MUSE_ERR_INVALID, "cg_maxiter must be >= 1");
+    return muse_implicit_H_columns_ex(c, seed, sim_begin, col_begin, col_end, theta0, atol, cg_maxiter, kCgReltolDefault, 0.0, 0, cols_out,
+                                      cg_iters_out);
+}
+
+int muse_implicit_H_batch_ex(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t sim_end, const double* theta0, double atol,
+                             int cg_maxiter, double cg_reltol, double cg_abstol, int flags, double* Hs_out, int32_t* cg_iters_out) {
     int rc = check_ctx(c);
     if (rc) return rc;
     if (!theta0 || !Hs_out) return fail(MUSE_ERR_INVALID, "NULL argument");
     if (sim_end < sim_begin || sim_begin < 0) return fail(MUSE_ERR_INVALID, "bad sim range");
-    if (cg_maxiter < 1) return fail(MUSE_ERR_INVALID, "cg_maxiter must be >= 1");
+    if (cg_maxiter < 0) return fail(MUSE_ERR_INVALID, "cg_maxiter must be >= 0");
     const int64_t nsims = sim_end - sim_begin;
     if (nsims == 0) return MUSE_OK;
     const int nt = c->ntheta;
@@ -2028,12 +2095,21 @@ int muse_implicit_H_batch(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t
     const int64_t slots = (int64_t)c->num_cus * 2 / (use_cluster(c) ? cluster_size(c) : 1);
     const bool per_column = nt > 1 && nsims * 2 <= slots;
     std::vector<double> cols((size_t)nsims * nt * nt);
-    rc = implicit_impl(c, seed, sim_begin, 0, nsims * nt, per_column, theta0, atol, cg_maxiter, cols.data(), cg_iters_out);
+    const CgOptions cg = {cg_maxiter, cg_reltol, cg_abstol, flags};
+    rc = implicit_impl(c, seed, sim_begin, 0, nsims * nt, per_column, theta0, atol, cg, cols.data(), cg_iters_out);
     if (rc) return rc;
     for (int64_t s = 0; s < nsims; ++s)
         for (int j = 0; j < nt; ++j)
             for (int i = 0; i < nt; ++i) Hs_out[(s * nt + i) * nt + j] = cols[((size_t)(s * nt + j)) * nt + i];
     return MUSE_OK;
+}
+
+int muse_implicit_H_batch(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t sim_end, const double* theta0, double atol,
+                          int cg_maxiter, double* Hs_out, int32_t* cg_iters_out) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (cg_maxiter < 1) return fail(MUSE_ERR_INVALID, "cg_maxiter must be >= 1");
+    return muse_implicit_H_batch_ex(c, seed, sim_begin, sim_end, theta0, atol, cg_maxiter, kCgReltolDefault, 0.0, 0, Hs_out, cg_iters_out);
 }
 
 }  // extern "C"

@@ -216,7 +216,15 @@ hipError_t launch_solver(const LaunchShape& s, const BatchArgs& a, hipStream_t s
 #ifdef MUSE_INSPECT  // development aid (tools/regs.py --check): instantiate ONE kernel, for a quick look at its assembly
     return launch_one<MUSE_INSPECT>(s, a, st);
 #elif defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_PAIR)   // ... of the two-parameter family: 2 ... kMaxTheta components, no big tier,
-    if (s.model != MUSE_MODEL_USER || s.big || s.implicit) return hipErrorInvalidValue;   // no implicit differentiation
+    if (s.model != MUSE_MODEL_USER || s.big) return hipErrorInvalidValue;
+    if (s.implicit) {   // implicit differentiation: a header that states its second derivatives (MUSE_MODEL_PAIR_SECOND)
+#ifdef MUSE_MODEL_PAIR_SECOND
+        return s.ntheta == 2 ? launch_place_implicit<UserModel<2>>(s, a, st) : s.ntheta <= 4 ? launch_place_implicit<UserModel<4>>(s, a, st)
+                                                                                             : launch_place_implicit<UserModel<kMaxTheta>>(s, a, st);
+#else
+        return hipErrorInvalidValue;  // (muse_engine.cpp refuses the call before it gets here)
+#endif
+    }
     return s.ntheta == 2 ? launch_place<UserModel<2>>(s, a, st) : s.ntheta <= 4 ? launch_place<UserModel<4>>(s, a, st)
                                                                                 : launch_place<UserModel<kMaxTheta>>(s, a, st);
 #elif defined(MUSE_USER_MODEL_HEADER)  // a library built from a user's model header holds that model only (user_model.hpp)

@@ -2126,8 +2126,11 @@ struct Solver : PairState<Model::kPair> {
 
     // What the implicit-differentiation H keeps of the draw in its extra vector: the simulation's true z (compiled-in models: x's
     // derivative in theta follows from it) or, for a user-supplied model, dx_i / dtheta_k itself (include/muse_model.h).
+    // (The two-parameter family needs TWO values per element, dx_i / da_k and dx_i / db_k, where the extra vector holds one: the
+    //  sampler's pass leaves the true z there, unused, and run_implicit_pair draws the element's normals again behind the solve.)
     __device__ __forceinline__ double keep_value(bool valid, double zt, double sd, const NormalPair& np, int i) const {
-        if constexpr (Model::kId == MUSE_MODEL_USER) return valid ? Model::dx_dtheta(sd, np.n1, np.n2, i) : 0.0;
+        if constexpr (Model::kPair) return zt;
+        else if constexpr (Model::kId == MUSE_MODEL_USER) return valid ? Model::dx_dtheta(sd, np.n1, np.n2, i) : 0.0;
         else return zt;
     }
 
@@ -2139,6 +2142,7 @@ struct Solver : PairState<Model::kPair> {
     // closed forms (see oracle/muse_oracle.c, mo_implicit_H, for the list).  Streaming policy only:
     // the CG vectors reuse the solver's g, s and history buffers; z_true sits in the extra vector.
     // Writes H[p] (row-major ntheta x ntheta) and the CG iteration count of column j to info[p*ntheta+j].
+    // (The two-parameter family has a branch of its own, run_implicit_pair below: the kernel picks it, kernels.hpp.)
     __device__ __forceinline__ void run_implicit(int p, double* wg_scratch, double* lds_x, double* lds_g) {
         begin<true>(p, wg_scratch, lds_x, lds_g);
         solve(p);
@@ -2318,6 +2322,136 @@ struct Solver : PairState<Model::kPair> {
             }
         }
     }
+
+#ifdef MUSE_MODEL_PAIR_SECOND
+    // The branch for the two-parameter family (include/muse_model.h, MUSE_MODEL_PAIR_SECOND): column j of H belongs to block
+    // j mod K and to parameter kind j / K (a or b).  With the header's q = {ozz, ozx, gza, gzb, sxa, sxb} and the draw's derivatives
+    // xa, xb, all at (x, zhat, theta0):
+    //   A w = -ozz w,   b = dFdtheta1[:, j] = -ozx x_kind (the column's block),   rows k and K + k of dFdtheta^T v = -sum gza v, -sum gzb v,
+    //   H1[k][j] = sum sxa x_kind,  H1[K + k][j] = sum sxb x_kind over the column's block (skipped when the caller says H1 is zero).
+    // The extra vector holds ONE value per element, so nothing kept of the draw is used: behind the solve a pass draws the normals again
+    // (the same generator sequence, so the same bits) and stores xa in the extra vector and xb in the fourth history vector, which
+    // the elementwise CG does not use -- the L-BFGS history is dead once the solve has ended -- together with ozz for the CG passes.
+    // CG stops at |r| <= max(cg_reltol |b|, cg_abstol) or after cg_maxiter iterations (0: H = H1).
+    __device__ __forceinline__ void run_implicit_pair(int p, double* wg_scratch, double* lds_x, double* lds_g) {
+        begin<true>(p, wg_scratch, lds_x, lds_g);
+        solve(p);
+        const int64_t ld = a.ld;
+        const int N = (int)a.N, nth = a.ntheta, K = nth >> 1;
+        VH xa, xb, xq, v, r, pp, Ap, t1;
+        xa.bind(extra, ld);
+        v.bind(wg_scratch + ld, ld);       // g buffer
+        r.bind(wg_scratch + 2 * ld, ld);   // s buffer
+        pp.bind(hist, ld);
+        Ap.bind(hist + ld, ld);
+        t1.bind(hist + 2 * ld, ld);
+        xb.bind(hist + 3 * ld, ld);
+        {
+            const uint64_t sim = (uint64_t)d.sim;
+            for_elems<T, EPT, 1>(ld, tfirst, ps(), [&](int jj, int i) {
+                const bool valid = i < N;  // phantom slots run the generator but keep zeros
+                const NormalPair np = normal_pair(a.seed, sim, (uint64_t)i);
+                double da, db, q[6];
+                Model::dx(gcoef(jj, i), np.n1, np.n2, da, db, i);
+                Model::second(gcoef(jj, i), x.get(jj, i), z.get(jj, i), q, i);
+                xa.set(jj, i, valid ? da : 0.0);
+                xb.set(jj, i, valid ? db : 0.0);
+                t1.set(jj, i, q[0]);
+            }, xa, xb, t1);
+        }
+        const int split = a.imp_split > 1 ? a.imp_split : 1;
+        const int plist = p + a.p0;  // position in the list that starts at sim_begin's first column
+        const int64_t psim = plist / split;
+        const int j_lo = split > 1 ? plist % split : 0, j_hi = split > 1 ? j_lo + 1 : nth;
+        const bool h1_zero = (a.imp_flags & 1) != 0;
+        for (int j = j_lo; j < j_hi; ++j) {
+            const int kb = j < K ? j : j - K;   // the column's block; its parameter kind selects the draw's derivative
+            xq.bind(j < K ? extra : hist + 3 * ld, ld);
+            // ---- right-hand side b = dFdtheta1[:, j]; v = 0, r = p = b --------------------------------
+            double sum[1] = {0.0}, mx[1] = {0.0};
+            for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
+                const double dxi = xq.get(jj, i);  // unconditional: the pair load is issued at the even element
+                double q[6];
+                Model::second(gcoef(jj, i), x.get(jj, i), z.get(jj, i), q, i);
+                const double bb = -(q[1] * dxi);
+                const double bi = blk(jj, i) == kb ? bb : 0.0;
+                v.set(jj, i, 0.0);
+                r.set(jj, i, bi);
+                pp.set(jj, i, bi);
+                sum[0] = fma(bi, bi, sum[0]);
+            }, v, r, pp);
+            reduce<1, 0>(sum, mx);
+            double rr = sum[0];
+            const double tol_rel = a.cg_reltol * __builtin_sqrt(rr);
+            const double tol = tol_rel > a.cg_abstol ? tol_rel : a.cg_abstol;
+            int it = 0;
+            while (it < a.cg_maxiter && !(__builtin_sqrt(rr) <= tol)) {
+                // ---- Ap = A_hess p, p.Ap -----------------------------------------------------------
+                double s1[1] = {0.0};
+                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
+                    const double pi = pp.get(jj, i);
+                    const double api = -(t1.get(jj, i) * pi);
+                    Ap.set(jj, i, api);
+                    s1[0] = fma(pi, api, s1[0]);
+                }, Ap);
+                reduce<1, 0>(s1, mx);
+                const double alpha = rr / s1[0];
+                // ---- v += alpha p ; r -= alpha Ap ; r.r ---------------------------------------------
+                double s2[1] = {0.0};
+                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
+                    v.set(jj, i, fma(alpha, pp.get(jj, i), v.get(jj, i)));
+                    const double ri = fma(-alpha, Ap.get(jj, i), r.get(jj, i));
+                    r.set(jj, i, ri);
+                    s2[0] = fma(ri, ri, s2[0]);
+                }, v, r);
+                reduce<1, 0>(s2, mx);
+                const double beta = s2[0] / rr;
+                rr = s2[0];
+                // ---- p = r + beta p -----------------------------------------------------------------
+                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
+                    pp.set(jj, i, fma(beta, pp.get(jj, i), r.get(jj, i)));
+                }, pp);
+                it += 1;
+            }
+            // ---- H[:, j] = H1[:, j] - dFdtheta^T v: rows k and K + k of every block, the two H1 sums of the column's block ----
+            double acc[MAXB], h1s[2] = {0.0, 0.0};
+#pragma unroll
+            for (int b = 0; b < MAXB; ++b) acc[b] = 0.0;
+            for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
+                const double vi = v.get(jj, i), dxi = xq.get(jj, i);
+                double q[6];
+                Model::second(gcoef(jj, i), x.get(jj, i), z.get(jj, i), q, i);
+                const double ta = -q[2], tb = -q[3];   // dFdtheta[i][k], dFdtheta[i][K + k]
+                const int k = blk(jj, i);
+#pragma unroll
+                for (int b = 0; b < MAXB; ++b) acc[b] = (k == b) ? fma(ta, vi, acc[b]) : ((k + K == b) ? fma(tb, vi, acc[b]) : acc[b]);
+                if (!h1_zero) {
+                    h1s[0] = k == kb ? fma(q[4], dxi, h1s[0]) : h1s[0];
+                    h1s[1] = k == kb ? fma(q[5], dxi, h1s[1]) : h1s[1];
+                }
+            });
+            reduce<MAXB, 0>(acc, mx);
+            if (!h1_zero) reduce<2, 0>(h1s, mx);
+            if (tid == 0 && crank == 0) {
+#pragma unroll
+                for (int b = 0; b < MAXB; ++b) {
+                    if (b < nth) {
+                        const double h1 = b == kb ? h1s[0] : (b == kb + K ? h1s[1] : 0.0);
+                        a.scores[(psim * nth + b) * nth + j] = h1 - acc[b];
+                    }
+                }
+                muse_info inf;
+                inf.iterations = it;
+                inf.f_calls = f_calls;
+                inf.status = status;
+                inf.hist_words = hist_words;
+                inf.f_min = f;
+                inf.gnorm = gmax;
+                a.info[psim * nth + j] = inf;
+            }
+        }
+    }
+#endif
 
     // -- phase 3: zhat out, score grad_theta logLike(x, zhat, theta), solver info
     __device__ __forceinline__ void finish(int p) {

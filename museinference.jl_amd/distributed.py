@@ -283,15 +283,15 @@ class ShardedMuseProblem:
         return (np.ascontiguousarray(allrows[:, :G * nth].reshape(n, G, nth)),
                 self._rows_to_info(allrows[:, G * nth:].reshape(n * G, ninfo)).reshape(n, G))
 
-    def implicit_H_batch(self, rng, sim_begin, sim_end, theta0, *, atol=1e-1, cg_maxiter=100):
+    def implicit_H_batch(self, rng, sim_begin, sim_end, theta0, *, atol=1e-1, cg_maxiter=100, **cg):
         """get_H! implicit-differentiation branch (src/muse.jl:335-405), the (sim, column) units shared like the
-        finite-difference ones."""
+        finite-difference ones.  cg: cg_reltol, cg_abstol, H1_is_zero, passed on to the local problem."""
         nth = np.atleast_1d(theta0).size
         if hasattr(self.local, "implicit_H_columns"):
             ncol = (sim_end - sim_begin) * nth
             lo, hi = block_partition(0, ncol, self.world, self.rank)
             if hi > lo:
-                cols, its = self.local.implicit_H_columns(rng, sim_begin, lo, hi, theta0, atol=atol, cg_maxiter=cg_maxiter)
+                cols, its = self.local.implicit_H_columns(rng, sim_begin, lo, hi, theta0, atol=atol, cg_maxiter=cg_maxiter, **cg)
             else:
                 cols, its = np.zeros((0, nth)), np.zeros(0, dtype=np.int32)
             counts = [h - l for l, h in (block_partition(0, ncol, self.world, r) for r in range(self.world))]
@@ -302,7 +302,7 @@ class ShardedMuseProblem:
                     allrows[:, nth].astype(np.int32).reshape(n, nth))
         lo, hi = block_partition(sim_begin, sim_end, self.world, self.rank)
         if hi > lo:
-            Hs, its = self.local.implicit_H_batch(rng, lo, hi, theta0, atol=atol, cg_maxiter=cg_maxiter)
+            Hs, its = self.local.implicit_H_batch(rng, lo, hi, theta0, atol=atol, cg_maxiter=cg_maxiter, **cg)
         else:
             Hs, its = np.zeros((0, nth, nth)), np.zeros((0, nth), dtype=np.int32)
         counts = [block_partition(sim_begin, sim_end, self.world, r) for r in range(self.world)]

@@ -154,8 +154,9 @@ def check_model_consistency(prob, theta, rng=0, n_probe=6, step=1e-5, rtol=2e-5)
         grad_theta logLike       against central differences of logLike in every theta_k
                                  (the family identity of include/muse_model.h: the score assembled from B is the derivative),
 
-        the second derivatives of a header with MUSE_MODEL_SECOND (what the implicit-differentiation get_H! builds on) against
-                                 central differences of the header's own first-order functions (_check_second, "second"),
+        the second derivatives of a header with MUSE_MODEL_SECOND or MUSE_MODEL_PAIR_SECOND (what the implicit-differentiation
+                                 get_H! builds on) against central differences of the header's own first-order functions
+                                 (_check_second, _check_pair_second: "second"),
 
     and returns {"grad_z": worst residual, "grad_theta": worst residual, "noise_floor": ...} -- residuals relative to the larger
     of the gradient's size and 1; noise_floor: what the rounding of logLike (a sum of N terms) alone puts into such a
@@ -189,7 +190,10 @@ def check_model_consistency(prob, theta, rng=0, n_probe=6, step=1e-5, rtol=2e-5)
         res_t = max(res_t, abs((fp - fm) / (2 * step) - s[k]) / scale)
     out = {"grad_z": float(res_z), "grad_theta": float(res_t), "noise_floor": float(floor)}
     if getattr(prob, "user_model", None) is not None and getattr(prob, "has_second_derivatives", False):
-        out["second"] = _check_second(prob.model_eval, theta, np.asarray(x), z, n_probe, rtol)
+        if getattr(prob.user_model, "pair", False):
+            out["second"] = _check_pair_second(prob.model_eval, prob.model_eval_second, theta, np.asarray(x), z, n_probe, rtol)
+        else:
+            out["second"] = _check_second(prob.model_eval, theta, np.asarray(x), z, n_probe, rtol)
     for name in ("grad_z", "grad_theta"):
         assert out[name] <= rtol + floor, (f"model consistency: {name} differs from the finite difference of logLike by {out[name]:.3g} "
                                            f"(relative; tolerance {rtol:g} + noise floor {floor:.3g})")
@@ -222,5 +226,42 @@ def _check_second(model_eval, theta, x, z, n_probe, rtol, h=1e-5):
             res = abs(fd - e[name]) / max(1.0, abs(e[name]))
             assert res <= rtol, (f"model consistency: {name} of element {i} is {e[name]:.9g}, the finite difference of the header's "
                                  f"own functions gives {fd:.9g}")
+            worst = max(worst, res)
+    return float(worst)
+
+
+def _check_pair_second(model_eval, model_eval_second, theta, x, z, n_probe, rtol, h=1e-5):
+    """The second-derivative functions of a header of the two-parameter family (MUSE_MODEL_PAIR_SECOND, include/muse_model.h) against
+    central differences of the header's own first-order functions, element by element on the host (model_eval(a, b, x, z, n1, n2, i)
+    and model_eval_second of HipMuseProblem): ozz, ozx, gza, gzb = d grad / d(z, x, a, b); xa, xb = d x(a, b, n1, n2) / d(a, b);
+    sxa, sxb = d/dx of -1/2 d term / d(a, b), the objective term differenced in the parameter and then in x (a wider step: a second
+    difference).  Returns the worst residual (relative to the larger of the value's size and 1); AssertionError beyond rtol."""
+    import numpy as np
+    N, K = z.size, theta.size // 2
+    worst = 0.0
+    rs = np.random.RandomState(7)
+    for i in np.unique(np.linspace(0, N - 1, n_probe).astype(int)):
+        k = int(i * K // N)
+        a, b = float(theta[k]), float(theta[K + k])
+        xi, zi = float(x[i]), float(z[i])
+        n1, n2 = rs.randn(2)
+        ev = lambda a=a, b=b, xx=xi, zz=zi: model_eval(a, b, xx, zz, n1, n2, i)
+        e = model_eval_second(a, b, xi, zi, n1, n2, i)
+        hz, hx = h * max(1.0, abs(zi)), h * max(1.0, abs(xi))
+        ha, hb = h * max(1.0, abs(a)), h * max(1.0, abs(b))
+        cd = lambda key, p, m, d: (p[key] - m[key]) / (2 * d)
+        fd = {"ozz": cd("grad", ev(zz=zi + hz), ev(zz=zi - hz), hz), "ozx": cd("grad", ev(xx=xi + hx), ev(xx=xi - hx), hx),
+              "gza": cd("grad", ev(a=a + ha), ev(a=a - ha), ha), "gzb": cd("grad", ev(b=b + hb), ev(b=b - hb), hb),
+              "xa": cd("x", ev(a=a + ha), ev(a=a - ha), ha), "xb": cd("x", ev(b=b + hb), ev(b=b - hb), hb)}
+        w = 30.0      # the mixed differences of the term itself: steps of 3e-4 (truncation ~1e-7, rounding ~1e-9 of the term's size)
+        Hx, Ha, Hb = w * hx, w * ha, w * hb
+        s_a = lambda xx: -0.5 * cd("term", ev(a=a + Ha, xx=xx), ev(a=a - Ha, xx=xx), Ha)
+        s_b = lambda xx: -0.5 * cd("term", ev(b=b + Hb, xx=xx), ev(b=b - Hb, xx=xx), Hb)
+        fd["sxa"] = (s_a(xi + Hx) - s_a(xi - Hx)) / (2 * Hx)
+        fd["sxb"] = (s_b(xi + Hx) - s_b(xi - Hx)) / (2 * Hx)
+        for name, d in fd.items():
+            res = abs(d - e[name]) / max(1.0, abs(e[name]))
+            assert res <= rtol, (f"model consistency: {name} of element {i} is {e[name]:.9g}, the finite difference of the header's "
+                                 f"own functions gives {d:.9g}")
             worst = max(worst, res)
     return float(worst)

@@ -362,7 +362,7 @@ def get_H_(result, prob, theta0=None, *, fdm="central_fdm(3,1)", grad_z_logLike_
     """
     _note_ignored(pool=pool, progress=progress)
     if implicit_diff:
-        return _get_H_implicit(result, prob, theta0, rng, nsims, implicit_diff_cg_kwargs, skip_errors)
+        return _get_H_implicit(result, prob, theta0, rng, nsims, implicit_diff_cg_kwargs, skip_errors, implicit_diff_H1_is_zero)
     method = as_fdm(fdm)
     if method.q != 1:
         raise ValueError("get_H! differentiates once: fdm must be a first-derivative method (central_fdm(p, 1))")
@@ -431,10 +431,40 @@ def _fd_batched(prob, rng, nsims, theta0, m, step, atol, fid_mode):
     return Hs, info
 
 
-def _get_H_implicit(result, prob, theta0, rng, nsims, cg_kwargs, skip_errors):
+def _cg_keywords(cg_kwargs):
+    """implicit_diff_cg_kwargs (splatted into IterativeSolvers.cg by the reference, src/muse.jl:381) as the keywords of the
+    implicit_H_batch seam: maxiter, reltol, abstol; Pl only as the identity (None or an identity matrix: no preconditioners here).
+    Any other key is an error, never ignored."""
+    kw = dict(cg_kwargs or {})
+    out = {"cg_maxiter": int(kw.pop("maxiter", 100))}
+    if "reltol" in kw:
+        out["cg_reltol"] = float(kw.pop("reltol"))
+    if "abstol" in kw:
+        out["cg_abstol"] = float(kw.pop("abstol"))
+    if "Pl" in kw:
+        Pl = kw.pop("Pl")
+        if Pl is not None:
+            try:
+                P = np.asarray(Pl, dtype=np.float64)
+            except (TypeError, ValueError):
+                P = None
+            if P is None or P.ndim != 2 or P.shape[0] != P.shape[1] or not np.array_equal(P, np.eye(P.shape[0])):
+                raise ValueError("implicit_diff_cg_kwargs: Pl must be the identity (None or an identity matrix): preconditioners are "
+                                 "not supported")
+    if kw:
+        raise ValueError(f"implicit_diff_cg_kwargs: unsupported key(s) {sorted(kw)} (supported: maxiter, reltol, abstol, Pl = identity)")
+    return out
+
+
+def _get_H_implicit(result, prob, theta0, rng, nsims, cg_kwargs, skip_errors, H1_is_zero=False):
     """get_H! with implicit_diff=true (src/muse.jl:335-405): H = H1 - dFdθᵀ A⁻¹ dFdθ1 per sim, A⁻¹ by CG
-    (implicit_diff_cg_kwargs default (maxiter=100, Pl=I)); the fiducial MAP is solved to 1e-1 as the
-    reference hard-codes (src/muse.jl:344).  CG iteration counts go to metadata["implicit_diff_cg_hists"]."""
+    (implicit_diff_cg_kwargs default (maxiter=100, Pl=I); reltol and abstol are passed on); implicit_diff_H1_is_zero skips H1
+    (src/muse.jl:353); the fiducial MAP is solved to 1e-1 as the reference hard-codes (src/muse.jl:344).  CG iteration counts go to
+    metadata["implicit_diff_cg_hists"].  A keyword beyond atol and cg_maxiter reaches the problem only when it is given, so that a
+    problem whose seam does not know it says so instead of ignoring it."""
+    cg = _cg_keywords(cg_kwargs)
+    if H1_is_zero:
+        cg["H1_is_zero"] = True
     rng = int(_something(rng, result.rng, _default_rng()))
     theta0 = prob.standardize_theta(_something(theta0, result.theta))
     remaining = nsims - len(result.Hs)
@@ -443,8 +473,7 @@ def _get_H_implicit(result, prob, theta0, rng, nsims, cg_kwargs, skip_errors):
     if not hasattr(prob, "implicit_H_batch"):
         raise NotImplementedError("implicit_diff needs a problem with the implicit_H_batch seam")
     t0 = time.perf_counter()
-    maxiter = int((cg_kwargs or {}).get("maxiter", 100))
-    Hs, its = prob.implicit_H_batch(rng, 0, remaining, theta0, atol=1e-1, cg_maxiter=maxiter)
+    Hs, its = prob.implicit_H_batch(rng, 0, remaining, theta0, atol=1e-1, **cg)
     result.Hs = list(result.Hs) + list(Hs)
     result.metadata.setdefault("implicit_diff_cg_hists", []).extend(list(its))
     result.H = np.mean(np.array(result.Hs), axis=0)

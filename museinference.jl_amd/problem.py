@@ -224,7 +224,7 @@ class HipMuseProblem(AbstractMuseProblem):
     @property
     def has_second_derivatives(self):
         """Whether the implicit-differentiation get_H! accepts this problem's model: the built-in models, and a user-supplied
-        header that defines MUSE_MODEL_SECOND (include/muse_model.h)."""
+        header that defines MUSE_MODEL_SECOND -- in the two-parameter family MUSE_MODEL_PAIR_SECOND -- (include/muse_model.h)."""
         return bool(self._lib.muse_model_has_second())
 
     def model_eval(self, iv, sd, x, z, n1, n2, i=0):
@@ -238,6 +238,15 @@ class HipMuseProblem(AbstractMuseProblem):
             # a header of the two-parameter family (include/muse_model.h, MUSE_MODEL_PAIR): `iv` and `sd` were the block's parameters a, b
             return dict(zip(("grad", "term", "t0", "c0", "c1", "c2", "c3", "z", "x", "C", "t1"), out.tolist()))
         return dict(zip(("grad", "term", "B", "ozz", "ozx", "bz", "bx", "z", "x", "dx_dsd"), out.tolist()))
+
+    def model_eval_second(self, a, b, x, z, n1, n2, i=0):
+        """The second derivatives of a header of the two-parameter family (MUSE_MODEL_PAIR_SECOND, include/muse_model.h) at one element
+        of a block with parameters a, b, evaluated on the host (muse_model_eval_pair_second): a dict with ozz, ozx, gza, gzb, sxa, sxb
+        at (x, z) and xa, xb of the draw at (n1, n2).  What check_model_consistency differentiates numerically."""
+        out = np.empty(8)
+        self._check(self._lib.muse_model_eval_pair_second(self._ctx, float(a), float(b), float(x), float(z), float(n1), float(n2), int(i),
+                                                          _capi.ptr(out)))
+        return dict(zip(("ozz", "ozx", "gza", "gzb", "sxa", "sxb", "xa", "xb"), out.tolist()))
 
     def close(self):
         if getattr(self, "_ctx", None):
@@ -532,15 +541,24 @@ class HipMuseProblem(AbstractMuseProblem):
                                                      _capi.ptr(Hs), _capi.ptr(info)))
         return Hs, info
 
-    def implicit_H_batch(self, rng, sim_begin, sim_end, theta0, *, atol=1e-1, cg_maxiter=100):
+    @staticmethod
+    def _cg_options(cg_reltol, cg_abstol, H1_is_zero):
+        return (float(np.sqrt(np.finfo(np.float64).eps)) if cg_reltol is None else float(cg_reltol), float(cg_abstol),
+                _capi.IMPLICIT_H1_IS_ZERO if H1_is_zero else 0)
+
+    def implicit_H_batch(self, rng, sim_begin, sim_end, theta0, *, atol=1e-1, cg_maxiter=100, cg_reltol=None, cg_abstol=0.0,
+                         H1_is_zero=False):
         """get_H! implicit-differentiation branch for sims [sim_begin, sim_end): (Hs [nsims, nθ, nθ],
-        cg iteration counts [nsims, nθ])   [src/muse.jl:335-405]"""
+        cg iteration counts [nsims, nθ])   [src/muse.jl:335-405].  Conjugate gradients stop at |r| <= max(cg_reltol |b|, cg_abstol)
+        (default sqrt(eps), 0) or after cg_maxiter iterations; H1_is_zero skips the H1 term (implicit_diff_H1_is_zero).  Values other
+        than the defaults are honoured for models of the two-parameter family and refused for every other model."""
         th = self._theta(theta0)
         ns = sim_end - sim_begin
         Hs = np.empty((ns, self.ntheta, self.ntheta))
         its = np.zeros((ns, self.ntheta), dtype=np.int32)
-        self._check(self._lib.muse_implicit_H_batch(self._ctx, _seed_of(rng), sim_begin, sim_end, _capi.ptr(th),
-                                                    float(atol), int(cg_maxiter), _capi.ptr(Hs), _capi.ptr(its)))
+        reltol, abstol, flags = self._cg_options(cg_reltol, cg_abstol, H1_is_zero)
+        self._check(self._lib.muse_implicit_H_batch_ex(self._ctx, _seed_of(rng), sim_begin, sim_end, _capi.ptr(th), float(atol),
+                                                       int(cg_maxiter), reltol, abstol, flags, _capi.ptr(Hs), _capi.ptr(its)))
         return Hs, its
 
     def fd_jacobian_columns(self, rng, sim_begin, col_begin, col_end, theta0, step, *, atol=1e-2, fid_mode=0,
@@ -579,14 +597,17 @@ class HipMuseProblem(AbstractMuseProblem):
                                                      _capi.ptr(F), _capi.ptr(info)))
         return F, info
 
-    def implicit_H_columns(self, rng, sim_begin, col_begin, col_end, theta0, *, atol=1e-1, cg_maxiter=100):
+    def implicit_H_columns(self, rng, sim_begin, col_begin, col_end, theta0, *, atol=1e-1, cg_maxiter=100, cg_reltol=None,
+                           cg_abstol=0.0, H1_is_zero=False):
         """The same column range for the implicit-differentiation H: (cols [n, nθ], cg iteration counts [n])."""
         th = self._theta(theta0)
         n = col_end - col_begin
         cols = np.empty((n, self.ntheta))
         its = np.zeros(n, dtype=np.int32)
-        self._check(self._lib.muse_implicit_H_columns(self._ctx, _seed_of(rng), sim_begin, col_begin, col_end, _capi.ptr(th),
-                                                      float(atol), int(cg_maxiter), _capi.ptr(cols), _capi.ptr(its)))
+        reltol, abstol, flags = self._cg_options(cg_reltol, cg_abstol, H1_is_zero)
+        self._check(self._lib.muse_implicit_H_columns_ex(self._ctx, _seed_of(rng), sim_begin, col_begin, col_end, _capi.ptr(th),
+                                                         float(atol), int(cg_maxiter), reltol, abstol, flags, _capi.ptr(cols),
+                                                         _capi.ptr(its)))
         return cols, its
 
     # -- exchange between ranks (C1-C3 of SURVEY.md §2) through the C ABI, for hosts without torch.distributed
