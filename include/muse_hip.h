@@ -28,7 +28,9 @@
  *                      k(i) = floor(i*ntheta/N).  ntheta = 1 is the reference's funnel
  *                      (src/simple.jl:59-73, docs/src/index.md:154-168).
  *   MUSE_MODEL_NOISE   z_i ~ N(0,1), x_i ~ N(z_i, e^theta); ntheta = 1.
- *   MUSE_MODEL_SMOOTH  z as FUNNEL, x = A z + n with A the periodic (1/4,1/2,1/4) stencil.
+ *   MUSE_MODEL_SMOOTH  z as FUNNEL, x = A z + n with A the periodic (1/4,1/2,1/4) stencil -- or, after muse_set_stencil, the
+ *                      periodic symmetric 3-tap operator (A z)_i = w1 (z_{i-1} + z_{i+1}) + w0 z_i of the context's weights:
+ *                      the one coupled latent model (a non-diagonal Hessian in z) of the HIP path.
  *   MUSE_MODEL_USER    a user-supplied elementwise model (the closures of SimpleMuseProblem as compiled code): three C
  *                      functions in a header (include/muse_model.h: the joint draw, d(-logLike)/dz with the objective's
  *                      element term, the score's element term) compiled into an engine library of its own, which exports
@@ -134,6 +136,19 @@ int muse_placement_info(muse_ctx* ctx, int* threads, int* workgroups_per_element
  * One set per model library and process is installed at a time; a context re-installs its own before it launches if another
  * context of the library has installed others since.  Libraries whose model declares no constants refuse the call. */
 int muse_set_constants(muse_ctx* ctx, int k, const double* values, int64_t count, int mem);
+/* The operator of MUSE_MODEL_SMOOTH as context state: (A z)_i = w[1] (z_{i-1} + z_{i+1}) + w[0] z_i, periodic -- another blur
+ * width, a differencing operator, negative side lobes, or w = {1, 0}: no coupling, the funnel written as a stencil.  Any finite
+ * pair is legal.  Once set, EVERY entry point that takes the context uses the weights (per-simulation operators, batched / multi
+ * / gathered maps, both get_H! branches, muse_run*): each launch carries its own copy and runs the kernels that read them, so
+ * contexts with different weights may be in flight together and the call waits for nothing.  Each stencil expression has the
+ * built-in's shape and operand order, fma(w1, zl + zr, w0 * z0): at w = {0.5, 0.25} the results are the built-in's bit for bit.
+ * w = NULL: back to the built-in stencil AND its kernels (literal weights); a context on which this was never called launches
+ * exactly those.  MUSE_ERR_INVALID: another model, a library built from a user's model header, a weight that is not finite
+ * (the context keeps the operator it had). */
+int muse_set_stencil(muse_ctx* ctx, const double* w /* {w0, w1}, or NULL: the built-in stencil and its kernels */);
+/* The operator in use: w_out[2] = {w0, w1} ({0.5, 0.25} for the built-in), *runtime_out = 1 when the weights were set (the launches
+ * read them) and 0 for the built-in kernels; either pointer may be NULL.  MUSE_ERR_INVALID for another model. */
+int muse_get_stencil(muse_ctx* ctx, double* w_out, int* runtime_out);
 /* The functions of a user-supplied model's header evaluated on the HOST for one element (include/muse_model.h) -- what the
  * reference gets from AD for free has to be checkable for hand-written derivatives (src/simple.jl:84-85): Python's
  * check_model_consistency differentiates these values numerically.  out[10] = { muse_model_grad's return value, the objective

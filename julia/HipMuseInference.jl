@@ -245,6 +245,17 @@ muse_run_sharded(prob::HipMuseProblem, seed::Integer, θ₀; kw...) = _native_lo
 # whose header declares run-time constants (include/muse_model.h, muse_const): vector k, one entry per element.
 set_constants(prob::HipMuseProblem, k::Integer, values::Vector{Float64}) =
     check(ccall((:muse_set_constants, libmuse_hip), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Int64, Cint), prob.ctx, k, values, length(values), MEM_HOST))
+# The operator of the "smooth" model as state of the problem (include/muse_hip.h: muse_set_stencil): (A z)_i = w1 (z_{i-1} + z_{i+1})
+# + w0 z_i, periodic, any finite pair -- used by every operator, map and get_H! branch from the next call on; `nothing`: back to the
+# built-in (1/2, 1/4) stencil and its kernels.
+set_stencil(prob::HipMuseProblem, w::Union{Nothing,NTuple{2,Real}}) =
+    check(ccall((:muse_set_stencil, libmuse_hip), Cint, (Ptr{Cvoid}, Ptr{Float64}), prob.ctx,
+                w === nothing ? C_NULL : Float64[w[1], w[2]]))
+function get_stencil(prob::HipMuseProblem)
+    w = Vector{Float64}(undef, 2); rt = Ref{Cint}(0)
+    check(ccall((:muse_get_stencil, libmuse_hip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cint}), prob.ctx, w, rt))
+    (; weights=(w[1], w[2]), runtime=rt[] != 0)
+end
 # plain maps over simulations the context has drawn before load their standard normals instead of generating them: off / on
 set_normals_cache(prob::HipMuseProblem, enabled::Bool) =
     check(ccall((:muse_set_normals_cache, libmuse_hip), Cint, (Ptr{Cvoid}, Cint), prob.ctx, enabled))

@@ -15,6 +15,8 @@ constexpr int kMaxTheta = MUSE_MAX_THETA;
 constexpr int kBigTheta = MUSE_MAX_THETA_EXT;  // ntheta in (kMaxTheta, kBigTheta]: the "big" tier (BigTheta below)
 constexpr int kResultAreas = 4;
 constexpr int kMaxCluster = 16;
+constexpr int kStencilTaps = 3;                          // window of the stencil model's operator: symmetric, periodic
+constexpr int kStencilWeights = (kStencilTaps + 1) / 2;  // its distinct weights {w0, w1}: centre, then outwards
 constexpr int kClusterSlotDoubles = 2 * kMaxCluster * 8 * 2;  // two parities x members x 8 values x 2 granules
 constexpr int64_t kClusterMinN = 65536;  // N >= this: several workgroups cooperate on one problem
 constexpr int64_t kMaxResidentN = 10000;
@@ -164,7 +166,13 @@ struct BatchArgs {
     // launching context's device vectors and their lengths.  Per LAUNCH (round 5; a process-wide __device__ symbol before:
     // a launch of another context of the same library still in flight would have read the new owner's pointers).
     const double* consts[4];
-    long const_len[4];
+    union {
+        long const_len[4];
+        // ... or, kernarg segment only, the weights {w0, w1} of the stencil model's operator when they are context state
+        // (muse_set_stencil; models.hpp, SmoothTapsModel): per LAUNCH like the constants, and in the place of their lengths -- a
+        // library holds either the built-in models or a user's, and sizeof(BatchArgs) is where the loop kernels find LoopArgs
+        double taps[kStencilWeights];
+    };
     // kernarg segment only: gran_sys == 2 -- the sharded loop with a board per GPU in DEVICE memory (muse_comm.cpp: every rank's board
     // is mapped into every rank by hipIpc): an element's score granules are stored into EVERY rank's board (posted writes over xGMI),
     // each at this rank's row offset; gran itself is not used then
@@ -173,6 +181,7 @@ struct BatchArgs {
 };
 constexpr size_t kArgsConstsOffset = offsetof(BatchArgs, consts);
 static_assert(offsetof(BatchArgs, const_len) == kArgsConstsOffset + 4 * sizeof(const double*), "muse_const reads {pointers[4], lengths[4]}");
+static_assert(sizeof(double) * kStencilWeights <= sizeof(long) * 4 && offsetof(BatchArgs, taps) % 16 == 0, "the weights take the place of const_len: one aligned scalar load");
 static_assert(sizeof(BigTheta) <= sizeof(MapTheta) * kMaxMaps, "the big tier's tables take the place of maps[]");
 constexpr size_t kArgsHeadBytes = offsetof(BatchArgs, maps);  // what the kernel keeps in LDS
 static_assert(kArgsHeadBytes % 16 == 0 && offsetof(BatchArgs, cur) % 8 == 0, "LDS copy of the argument block");
@@ -299,15 +308,17 @@ struct LaunchShape {
     bool big;    // the big tier's instantiation (BigTheta): ntheta > kMaxTheta, or 2..kMaxTheta components of an elementwise model in a
                  // streaming placement (muse_engine.cpp, tier_big: the same bits, 2.4x faster than the small tiers' streaming passes)
     bool lds_s;  // stencil model in a cluster: the search direction in LDS (vec.hpp, LdsMirror)
+    bool taps;   // stencil model: the operator's weights are the launch's (BatchArgs::taps), not the built-in literals
     size_t lds;
     void* done_event;  // hipEvent_t (or null) that the launch itself signals on completion: no separate event packet
 };
 hipError_t launch_solver(const LaunchShape& s, const BatchArgs& a, hipStream_t stream);
-hipError_t launch_sample(int model, const BatchArgs& a, uint64_t sim, double* x, double* z, double* noise, hipStream_t stream);
+// (taps: the stencil model with the launch's own weights, BatchArgs::taps)
+hipError_t launch_sample(int model, bool taps, const BatchArgs& a, uint64_t sim, double* x, double* z, double* noise, hipStream_t stream);
 // the standard normals of ONE stream into a slot of the normals cache's layout ([2][ld]: n1, n2), drawn by the whole GPU instead of
 // by the one workgroup that solves the stream's problem (muse_engine.cpp, fd_values_impl: the fiducial MAP of get_H!)
 hipError_t launch_normals(uint64_t seed, uint64_t sim, int64_t ld, double* slot, hipStream_t stream);
-hipError_t launch_loglike(int model, const BatchArgs& a, const double* x, const double* z, double* g, double* out, hipStream_t stream);
+hipError_t launch_loglike(int model, bool taps, const BatchArgs& a, const double* x, const double* z, double* g, double* out, hipStream_t stream);
 // the device-resident loop: false where the placement has no loop kernel (cluster placements); max_grid = the number of
 // workgroups that are certainly resident at once (they meet at the end of every iteration)
 bool loop_supported(const LaunchShape& s);

@@ -66,8 +66,35 @@ struct SmoothModel {  // z as funnel, x = A z + n, A = periodic (1/4, 1/2, 1/4);
     using SCoef = double; using GCoef = double;
     static constexpr bool kStencil = true;
     static constexpr int kId = MUSE_MODEL_SMOOTH;
+    __device__ static __forceinline__ double w0() { return 0.5; }
+    __device__ static __forceinline__ double w1() { return 0.25; }
     __device__ static __forceinline__ double score_term(double, double z, int) { return z * z; }
 };
+// The same model with the operator's weights as context state (muse_set_stencil): A = periodic (w1, w0, w1), read as wavefront-uniform
+// scalars from the launch's own kernel-argument block (args.hpp, BatchArgs::taps), so that contexts with different weights may have
+// launches in flight together.  Every stencil expression is stencil_apply's, in the built-in's shape and operand order: at
+// (1/2, 1/4) these kernels give the built-in's bits.
+typedef __attribute__((address_space(4))) const double* kernarg_f64;
+template <int MAXB_>
+struct SmoothTapsModel {
+    static constexpr int MAXB = MAXB_;
+    static constexpr bool kPair = false;
+    using SCoef = double; using GCoef = double;
+    static constexpr bool kStencil = true;
+    static constexpr int kId = MUSE_MODEL_SMOOTH;
+    __device__ static __forceinline__ double w0() { return ((kernarg_f64)__builtin_amdgcn_kernarg_segment_ptr())[offsetof(BatchArgs, taps) / 8]; }
+    __device__ static __forceinline__ double w1() { return ((kernarg_f64)__builtin_amdgcn_kernarg_segment_ptr())[offsetof(BatchArgs, taps) / 8 + 1]; }
+    __device__ static __forceinline__ double score_term(double, double z, int) { return z * z; }
+};
+// (A z)_i of a stencil model from the element and its two neighbours: w1 (zl + zr) + w0 z0, the product rounded, then ONE fma
+// (stencil_fma: from the neighbours' sum, for a caller that loads the centre element behind it)
+template <class Model>
+__device__ __forceinline__ double stencil_fma(double zlr, double z0) {
+    if constexpr (Model::kStencil) return fma(Model::w1(), zlr, Model::w0() * z0);
+    else return 0.0;   // (never called: the elementwise models have no operator)
+}
+template <class Model>
+__device__ __forceinline__ double stencil_apply(double zl, double z0, double zr) { return stencil_fma<Model>(zl + zr, z0); }
 
 // Coefficients of an element's block for the models with TWO parameters per block (include/muse_model.h, MUSE_MODEL_PAIR): what the
 // draw takes (c[0], c[1]) and what the objective takes (all four).  The tables hold a block's coefficients side by side:

@@ -109,6 +109,10 @@ struct muse_ctx {
     double* consts_host[4] = {nullptr, nullptr, nullptr, nullptr};
     long consts_len[4] = {0, 0, 0, 0};
     bool has_consts = false;
+    // the stencil model's operator (muse_set_stencil): weights that travel with every launch and select the kernels that read them,
+    // or -- never set, or set back with NULL -- the built-in (1/4, 1/2, 1/4) and its kernels
+    bool stencil_taps = false;
+    double stencil_w[kStencilWeights] = {0.5, 0.25};
     bool nc_auto = true;                 // muse_set_normals_cache: plain maps may store / load the normals of repeated simulations
     double* fid_norm = nullptr;          // [2][ld]: the standard normals of get_H!'s fiducial stream, drawn by a kernel of its own (fd_values_impl)
     unsigned int* fid_flag = nullptr;    // device word: the tag of the last fiducial MAP published inside a finite-difference launch
@@ -430,6 +434,7 @@ static int launch_batch(muse_ctx* c, BatchArgs& a, hipEvent_t done = nullptr) {
         shape.model = c->model; shape.ntheta = c->ntheta; shape.place = pl; shape.grid = grid; shape.implicit = implicit; shape.lds = lds;
         shape.big = tier_big(c, pl, a.nmaps);
         shape.lds_s = !implicit && pl == P_C256 && stencil_lds_s(c, a.csize);
+        shape.taps = c->stencil_taps;
         shape.done_event = done;
         const hipError_t e = launch_solver(shape, a, c->lane->stream);
         if (e != hipSuccess) rc = fail(MUSE_ERR_HIP, std::string("solver launch: ") + hipGetErrorString(e));
@@ -525,6 +530,8 @@ static void set_launch_constants(const muse_ctx* c, BatchArgs& a) {
         a.consts[k] = c->consts_dev[k];
         a.const_len[k] = c->consts_len[k];
     }
+    if (c->stencil_taps)   // (the stencil model has no constants: the weights take the place of their lengths, args.hpp)
+        for (int k = 0; k < kStencilWeights; ++k) a.taps[k] = c->stencil_w[k];
 }
 
 extern "C" {
@@ -803,6 +810,37 @@ int muse_synchronize(muse_ctx* c) {
     if (rc) return rc;
     return drain_lanes(c);
 }
+int muse_set_stencil(muse_ctx* c, const double* w) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+#ifdef MUSE_USER_MODEL_HEADER
+    (void)w;
+    return fail(MUSE_ERR_INVALID, "muse_set_stencil: this library was built from a user's model header and holds no stencil model");
+#else
+    if (c->model != MUSE_MODEL_SMOOTH) return fail(MUSE_ERR_INVALID, "muse_set_stencil: the context's model is not MUSE_MODEL_SMOOTH");
+    if (!w) {   // back to the built-in operator and its kernels
+        c->stencil_taps = false;
+        c->stencil_w[0] = 0.5;
+        c->stencil_w[1] = 0.25;
+        return MUSE_OK;
+    }
+    for (int k = 0; k < kStencilWeights; ++k)
+        if (!isfinite(w[k])) return fail(MUSE_ERR_INVALID, "muse_set_stencil: the weights must be finite");
+    // (nothing to wait for: a launch in flight carries its own copy of the weights)
+    for (int k = 0; k < kStencilWeights; ++k) c->stencil_w[k] = w[k];
+    c->stencil_taps = true;
+    return MUSE_OK;
+#endif
+}
+int muse_get_stencil(muse_ctx* c, double* w_out, int* runtime_out) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (c->model != MUSE_MODEL_SMOOTH) return fail(MUSE_ERR_INVALID, "muse_get_stencil: the context's model is not MUSE_MODEL_SMOOTH");
+    if (w_out)
+        for (int k = 0; k < kStencilWeights; ++k) w_out[k] = c->stencil_w[k];
+    if (runtime_out) *runtime_out = c->stencil_taps ? 1 : 0;
+    return MUSE_OK;
+}
 int muse_set_constants(muse_ctx* c, int k, const double* values, int64_t count, int mem) {
 #if defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_NCONST)
     int rc = check_ctx(c);
@@ -1033,7 +1071,7 @@ int muse_sample_x_z(muse_ctx* c, uint64_t seed, int64_t sim, const double* theta
     base_args(c, a, theta);
     a.seed = seed;
     double *dx = c->tmp, *dz = c->tmp + c->ld, *dn = c->tmp + 2 * c->ld;
-    HIPCHK(launch_sample(c->model, a, (uint64_t)sim, dx, dz, dn, c->lane->stream));
+    HIPCHK(launch_sample(c->model, c->stencil_taps, a, (uint64_t)sim, dx, dz, dn, c->lane->stream));
     if (x_out) HIPCHK(hipMemcpyAsync(x_out, dx, (size_t)c->N * sizeof(double), out_kind(mem), c->lane->stream));
     if (z_out) HIPCHK(hipMemcpyAsync(z_out, dz, (size_t)c->N * sizeof(double), out_kind(mem), c->lane->stream));
     HIPCHK(hipStreamSynchronize(c->lane->stream));
@@ -1046,7 +1084,7 @@ static int run_loglike(muse_ctx* c, const double* x, const double* z, const doub
     double *dx = c->tmp, *dz = c->tmp + c->ld;
     HIPCHK(hipMemcpyAsync(dx, x, (size_t)c->N * sizeof(double), in_kind(mem), c->lane->stream));
     HIPCHK(hipMemcpyAsync(dz, z, (size_t)c->N * sizeof(double), in_kind(mem), c->lane->stream));
-    HIPCHK(launch_loglike(c->model, a, dx, dz, gdev, c->small_dev, c->lane->stream));
+    HIPCHK(launch_loglike(c->model, c->stencil_taps, a, dx, dz, gdev, c->small_dev, c->lane->stream));
     return MUSE_OK;
 }
 
@@ -1455,7 +1493,7 @@ static bool loop_usable(muse_ctx* c, int S, int64_t nlocal, LaunchShape* shape_o
     const int64_t nprob_total = (int64_t)S + 1;
     const int pl = choose_place(c);
     LaunchShape shape;
-    shape.model = c->model; shape.ntheta = nt; shape.place = pl; shape.grid = 0; shape.implicit = false; shape.lds_s = false;
+    shape.model = c->model; shape.ntheta = nt; shape.place = pl; shape.grid = 0; shape.implicit = false; shape.lds_s = false; shape.taps = false;
     shape.big = false;  // (the loop kernel runs the resident placements)
     shape.done_event = nullptr;
     const bool xg_lds = pl == P_R512x10;

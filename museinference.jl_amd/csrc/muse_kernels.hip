@@ -109,6 +109,17 @@ __global__ void __launch_bounds__(256) smooth_finish_kernel(int64_t N, const dou
     }
 }
 
+// (the stencil model with the launch's own weights: the argument block comes first, as in every kernel that reads BatchArgs::taps
+//  from its kernel-argument segment, and the expression is models.hpp's stencil_apply)
+__global__ void __launch_bounds__(256) smooth_finish_taps_kernel(BatchArgs a, const double* __restrict__ z, const double* __restrict__ noise,
+                                                                 double* __restrict__ x) {
+    const int64_t N = a.N;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t im = i == 0 ? N - 1 : i - 1, ip = i == N - 1 ? 0 : i + 1;
+        x[i] = stencil_apply<SmoothTapsModel<kMaxTheta>>(z[im], z[i], z[ip]) + noise[i];
+    }
+}
+
 // logLike and grad_z logLike (note the sign: the solver works with -logLike), plus the per-block score
 // sums; one workgroup, fixed-shape reduction (same element->thread map as the solver).
 template <class Model>
@@ -150,12 +161,12 @@ __global__ void __launch_bounds__(1024) loglike_kernel(BatchArgs a, const double
             const int ic = valid ? i : 0;
             const int im2 = wrap(ic - 2), im1 = wrap(ic - 1), ip1 = wrap(ic + 1), ip2 = wrap(ic + 2);
             const double zm2 = zin[im2], zm1 = zin[im1], z0 = zin[ic], zp1 = zin[ip1], zp2 = zin[ip2];
-            const double rm = xin[im1] - fma(0.25, zm2 + z0, 0.5 * zm1);
-            const double r0 = xin[ic] - fma(0.25, zm1 + zp1, 0.5 * z0);
-            const double rp = xin[ip1] - fma(0.25, z0 + zp2, 0.5 * zp1);
+            const double rm = xin[im1] - stencil_apply<Model>(zm2, zm1, z0);
+            const double r0 = xin[ic] - stencil_apply<Model>(zm1, z0, zp1);
+            const double rp = xin[ip1] - stencil_apply<Model>(z0, zp1, zp2);
             const double t = ivk * z0;
             sum[0] = valid ? fma(t, z0, fma(r0, r0, sum[0])) : sum[0];
-            gi = valid ? t - fma(0.25, rm + rp, 0.5 * r0) : 0.0;
+            gi = valid ? t - stencil_apply<Model>(rm, r0, rp) : 0.0;
         } else {
             gi = Model::grad(ivk, xin[i], zin[i], sum[0], i);
         }
@@ -244,6 +255,8 @@ hipError_t launch_solver(const LaunchShape& s, const BatchArgs& a, hipStream_t s
     if (s.big) {  // the big tier (args.hpp, BigTheta; muse_engine.cpp, tier_big): streaming placements only
         if (s.model == MUSE_MODEL_FUNNEL)
             return s.implicit ? launch_place_implicit<FunnelModel<kBigTheta>>(s, a, st) : launch_place_big<FunnelModel<kBigTheta>>(s, a, st);
+        if (s.model == MUSE_MODEL_SMOOTH && s.taps)
+            return s.implicit ? launch_place_implicit<SmoothTapsModel<kBigTheta>>(s, a, st) : launch_place_big<SmoothTapsModel<kBigTheta>>(s, a, st);
         if (s.model == MUSE_MODEL_SMOOTH)
             return s.implicit ? launch_place_implicit<SmoothModel<kBigTheta>>(s, a, st) : launch_place_big<SmoothModel<kBigTheta>>(s, a, st);
         return hipErrorInvalidValue;
@@ -255,6 +268,10 @@ hipError_t launch_solver(const LaunchShape& s, const BatchArgs& a, hipStream_t s
                    : nt == 2 ? launch_place_implicit<FunnelModel<2>>(s, a, st)
                    : nt <= 4 ? launch_place_implicit<FunnelModel<4>>(s, a, st)
                              : launch_place_implicit<FunnelModel<kMaxTheta>>(s, a, st);
+        if (s.taps)
+            return nt <= 2   ? launch_place_implicit<SmoothTapsModel<2>>(s, a, st)
+                   : nt <= 4 ? launch_place_implicit<SmoothTapsModel<4>>(s, a, st)
+                             : launch_place_implicit<SmoothTapsModel<kMaxTheta>>(s, a, st);
         return nt <= 2   ? launch_place_implicit<SmoothModel<2>>(s, a, st)
                : nt <= 4 ? launch_place_implicit<SmoothModel<4>>(s, a, st)
                          : launch_place_implicit<SmoothModel<kMaxTheta>>(s, a, st);
@@ -265,6 +282,10 @@ hipError_t launch_solver(const LaunchShape& s, const BatchArgs& a, hipStream_t s
                : nt == 2 ? launch_place<FunnelModel<2>>(s, a, st)
                : nt <= 4 ? launch_place<FunnelModel<4>>(s, a, st)
                          : launch_place<FunnelModel<kMaxTheta>>(s, a, st);
+    if (s.taps)
+        return nt <= 2   ? launch_place<SmoothTapsModel<2>>(s, a, st)
+               : nt <= 4 ? launch_place<SmoothTapsModel<4>>(s, a, st)
+                         : launch_place<SmoothTapsModel<kMaxTheta>>(s, a, st);
     return nt <= 2   ? launch_place<SmoothModel<2>>(s, a, st)
            : nt <= 4 ? launch_place<SmoothModel<4>>(s, a, st)
                      : launch_place<SmoothModel<kMaxTheta>>(s, a, st);
@@ -386,11 +407,11 @@ hipError_t launch_normals(uint64_t seed, uint64_t sim, int64_t ld, double* slot,
     return hipGetLastError();
 }
 
-hipError_t launch_sample(int model, const BatchArgs& a, uint64_t sim, double* x, double* z, double* noise, hipStream_t st) {
+hipError_t launch_sample(int model, bool taps, const BatchArgs& a, uint64_t sim, double* x, double* z, double* noise, hipStream_t st) {
     const int grid = (int)((a.N + 255) / 256 < 4096 ? (a.N + 255) / 256 : 4096);
 #ifdef MUSE_USER_MODEL_HEADER
     (void)noise;
-    if (model != MUSE_MODEL_USER) return hipErrorInvalidValue;
+    if (model != MUSE_MODEL_USER || taps) return hipErrorInvalidValue;
     hipLaunchKernelGGL(sample_user_kernel, dim3(grid), dim3(256), 0, st, a, sim, x, z);
     return hipGetLastError();
 #endif
@@ -398,14 +419,15 @@ hipError_t launch_sample(int model, const BatchArgs& a, uint64_t sim, double* x,
     else if (model == MUSE_MODEL_FUNNEL) hipLaunchKernelGGL(sample_kernel<MUSE_MODEL_FUNNEL>, dim3(grid), dim3(256), 0, st, a, sim, x, z);
     else {
         hipLaunchKernelGGL(sample_kernel<MUSE_MODEL_SMOOTH>, dim3(grid), dim3(256), 0, st, a, sim, noise, z);
-        hipLaunchKernelGGL(smooth_finish_kernel, dim3(grid), dim3(256), 0, st, a.N, z, noise, x);
+        if (taps) hipLaunchKernelGGL(smooth_finish_taps_kernel, dim3(grid), dim3(256), 0, st, a, z, noise, x);
+        else hipLaunchKernelGGL(smooth_finish_kernel, dim3(grid), dim3(256), 0, st, a.N, z, noise, x);
     }
     return hipGetLastError();
 }
 
-hipError_t launch_loglike(int model, const BatchArgs& a, const double* x, const double* z, double* g, double* out, hipStream_t st) {
+hipError_t launch_loglike(int model, bool taps, const BatchArgs& a, const double* x, const double* z, double* g, double* out, hipStream_t st) {
 #ifdef MUSE_USER_MODEL_HEADER
-    if (model != MUSE_MODEL_USER) return hipErrorInvalidValue;
+    if (model != MUSE_MODEL_USER || taps) return hipErrorInvalidValue;
 #ifdef MUSE_MODEL_PAIR
     if (a.ntheta > kMaxTheta) return hipErrorInvalidValue;
 #else
@@ -418,6 +440,8 @@ hipError_t launch_loglike(int model, const BatchArgs& a, const double* x, const 
     if (model == MUSE_MODEL_NOISE) hipLaunchKernelGGL(loglike_kernel<NoiseModel>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
     else if (model == MUSE_MODEL_FUNNEL && a.ntheta > kMaxTheta) hipLaunchKernelGGL(loglike_kernel<FunnelModel<kBigTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
     else if (model == MUSE_MODEL_FUNNEL) hipLaunchKernelGGL(loglike_kernel<FunnelModel<kMaxTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
+    else if (taps && a.ntheta > kMaxTheta) hipLaunchKernelGGL(loglike_kernel<SmoothTapsModel<kBigTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
+    else if (taps) hipLaunchKernelGGL(loglike_kernel<SmoothTapsModel<kMaxTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
     else if (a.ntheta > kMaxTheta) hipLaunchKernelGGL(loglike_kernel<SmoothModel<kBigTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
     else hipLaunchKernelGGL(loglike_kernel<SmoothModel<kMaxTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
     return hipGetLastError();

@@ -375,14 +375,14 @@ struct Solver : PairState<Model::kPair> {
         auto wrap = [&](int k) { return k < 0 ? k + N : (k >= N ? k - N : k); };
         const int im2 = wrap(i - 2), im1 = wrap(i - 1), ip1 = wrap(i + 1), ip2 = wrap(i + 2);
         const double zm2 = zt(im2), zm1 = zt(im1), z0 = zt(i), zp1 = zt(ip1), zp2 = zt(ip2);
-        const double rm = x.get1(im1) - fma(0.25, zm2 + z0, 0.5 * zm1);
-        const double r0 = x.get1(i) - fma(0.25, zm1 + zp1, 0.5 * z0);
-        const double rp = x.get1(ip1) - fma(0.25, z0 + zp2, 0.5 * zp1);
+        const double rm = x.get1(im1) - stencil_apply<Model>(zm2, zm1, z0);
+        const double r0 = x.get1(i) - stencil_apply<Model>(zm1, z0, zp1);
+        const double rp = x.get1(ip1) - stencil_apply<Model>(z0, zp1, zp2);
         const double t = this->ivk(0, i) * z0;
         t_out = t;
         z_out = z0;
         r_out = r0;
-        return t - fma(0.25, rm + rp, 0.5 * r0);
+        return t - stencil_apply<Model>(rm, r0, rp);
     }
 
     // ---- stencil model, pair-wise --------------------------------------------------------------
@@ -454,13 +454,13 @@ struct Solver : PairState<Model::kPair> {
                 double xL = dpp_move<kDppWaveShr1>(xp.b), xR = dpp_move<kDppWaveShl1>(xp.a);
                 if (lane == 0) { ztL = ze; xL = xe; }
                 if (lane == 63) { ztR = ze; xR = xe; }
-                const double rm = xL - fma(0.25, ztL.a + ztp.a, 0.5 * ztL.b);    // r at i0-1
-                const double r0 = xp.a - fma(0.25, ztL.b + ztp.b, 0.5 * ztp.a);  // r at i0
-                const double r1 = xp.b - fma(0.25, ztp.a + ztR.a, 0.5 * ztp.b);  // r at i0+1
-                const double r2 = xR - fma(0.25, ztp.b + ztR.b, 0.5 * ztR.a);    // r at i0+2
+                const double rm = xL - stencil_apply<Model>(ztL.a, ztL.b, ztp.a);    // r at i0-1
+                const double r0 = xp.a - stencil_apply<Model>(ztL.b, ztp.a, ztp.b);  // r at i0
+                const double r1 = xp.b - stencil_apply<Model>(ztp.a, ztp.b, ztR.a);  // r at i0+1
+                const double r2 = xR - stencil_apply<Model>(ztp.b, ztR.a, ztR.b);    // r at i0+2
                 const double t0 = ivk(0, i0) * ztp.a, t1 = ivk(1, i0 + 1) * ztp.b;
-                g0[u] = t0 - fma(0.25, rm + r1, 0.5 * r0);
-                g1[u] = t1 - fma(0.25, r0 + r2, 0.5 * r1);
+                g0[u] = t0 - stencil_apply<Model>(rm, r0, r1);
+                g1[u] = t1 - stencil_apply<Model>(r0, r1, r2);
                 tt[u][0] = t0; zz[u][0] = ztp.a; rr[u][0] = r0;
                 tt[u][1] = t1; zz[u][1] = ztp.b; rr[u][1] = r1;
             }
@@ -1603,7 +1603,8 @@ struct Solver : PairState<Model::kPair> {
                     const bool valid = i < N;
                     const int ic = valid ? i : 0;
                     const int im = ic == 0 ? (int)N - 1 : ic - 1, ip = ic == (int)N - 1 ? 0 : ic + 1;
-                    const double az = fma(0.25, g.get1(im) + g.get1(ip), 0.5 * g.get1(ic));
+                    const double zl = g.get1(im), zr = g.get1(ip);
+                    const double az = stencil_apply<Model>(zl, g.get1(ic), zr);
                     const double xv = az + x.get(jj, i);
                     x.set(jj, i, valid ? xv : 0.0);
                 }, x);
@@ -2156,11 +2157,12 @@ struct Solver : PairState<Model::kPair> {
         Ap.bind(hist + ld, ld);
         t1.bind(hist + 2 * ld, ld);
         t2.bind(hist + 3 * ld, ld);
-        auto Aat = [&](const VH& w, int i) {  // (A w)_i, periodic (1/4, 1/2, 1/4); the pad element maps to 0
+        auto Aat = [&](const VH& w, int i) {  // (A w)_i, the periodic stencil (models.hpp, stencil_apply); the pad element maps to 0
             const bool valid = i < N;
             const int ic = valid ? i : 0;
             const int im = ic == 0 ? N - 1 : ic - 1, ip = ic == N - 1 ? 0 : ic + 1;
-            const double a0 = fma(0.25, w.get1(im) + w.get1(ip), 0.5 * w.get1(ic));
+            const double lr = w.get1(im) + w.get1(ip);
+            const double a0 = stencil_fma<Model>(lr, w.get1(ic));
             return valid ? a0 : 0.0;
         };
         // imp_split == ntheta: this element is ONE column of one simulation's H (few simulations, many theta: the

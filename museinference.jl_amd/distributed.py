@@ -139,6 +139,14 @@ class ShardedMuseProblem:
     def __getattr__(self, name):
         return getattr(self.local, name)
 
+    def set_stencil(self, weights):
+        """The "smooth" model's operator weights (HipMuseProblem.set_stencil) on this rank's problem: every rank calls it with the
+        same weights -- they are state of the rank's own context, nothing is exchanged."""
+        return self.local.set_stencil(weights)
+
+    def get_stencil(self):
+        return self.local.get_stencil()
+
     # -- the muse! outer loop in the library's native code, sharded (muse_run_sharded of the C ABI): with the engine's own
     #    communicator every rank runs the loop itself -- one gathered map per iteration, the same step on every rank --
     #    and no Python, torch tensor or allocation sits between two maps.  Without it muse_() drives the maps from Python.

@@ -185,8 +185,10 @@ class HipMuseProblem(AbstractMuseProblem):
     supports_native_muse = True  # muse_() may hand the whole outer loop to muse_run (class attribute: wrappers
                                  # that forward attribute access to a HipMuseProblem do not inherit it)
 
-    def __init__(self, x, model="funnel", ntheta=1, prior=None, device=0, N=None, constants=None):
-        """constants: {"P": array of N doubles, ...} for a user model written with run-time constants
+    def __init__(self, x, model="funnel", ntheta=1, prior=None, device=0, N=None, constants=None, stencil=None):
+        """stencil: (w0, w1) -- model="smooth" only -- the weights of the operator (A z)_i = w1 (z_{i-1} + z_{i+1}) + w0 z_i in place
+        of the built-in (1/2, 1/4); set_stencil changes them later.
+        constants: {"P": array of N doubles, ...} for a user model written with run-time constants
         (ElementwiseModel.from_source(..., runtime_constants=["P", ...]); include/muse_model.h, muse_const) -- what the
         reference's SimpleMuseProblem closures capture; set_constants replaces a vector later, without rebuilding anything."""
         from .models import ElementwiseModel
@@ -211,8 +213,14 @@ class HipMuseProblem(AbstractMuseProblem):
         self._ctx = ctx
         if self.x is not None:
             self._check(self._lib.muse_set_data(self._ctx, _capi.ptr(self.x), _capi.MEM_HOST))
-        for name, values in (constants or {}).items():
-            self.set_constants(name, values)
+        try:
+            for name, values in (constants or {}).items():
+                self.set_constants(name, values)
+            if stencil is not None:
+                self.set_stencil(stencil)
+        except Exception:
+            self.close()        # (a refused option: the context that was just created does not outlive the error)
+            raise
 
     def set_constants(self, name, values):
         """Run-time constant vector `name` (or its index) of the user model: N finite doubles (muse_set_constants)."""
@@ -220,6 +228,23 @@ class HipMuseProblem(AbstractMuseProblem):
         k = names.index(name) if isinstance(name, str) else int(name)
         v = _capi.f8(values, self.N)
         self._check(self._lib.muse_set_constants(self._ctx, k, _capi.ptr(v), v.size, _capi.MEM_HOST))
+
+    def set_stencil(self, weights):
+        """The operator of the "smooth" model as context state (muse_set_stencil): weights = (w0, w1), any finite pair, for the
+        periodic (A z)_i = w1 (z_{i-1} + z_{i+1}) + w0 z_i -- every operator, map, get_H! branch and muse() of this problem uses
+        them from the next call on; None: back to the built-in (1/2, 1/4) stencil and its kernels.  At (0.5, 0.25) the results are
+        the built-in's bit for bit; (1, 0) is the funnel."""
+        if weights is None:
+            self._check(self._lib.muse_set_stencil(self._ctx, None))
+            return
+        w = _capi.f8(weights, 2)
+        self._check(self._lib.muse_set_stencil(self._ctx, _capi.ptr(w)))
+
+    def get_stencil(self):
+        """((w0, w1), runtime): the operator's weights and whether they were set (False: the built-in stencil's kernels run)."""
+        w, rt = np.empty(2), C.c_int()
+        self._check(self._lib.muse_get_stencil(self._ctx, _capi.ptr(w), C.byref(rt)))
+        return (float(w[0]), float(w[1])), bool(rt.value)
 
     @property
     def has_second_derivatives(self):
@@ -734,7 +759,7 @@ class PositiveThetaProblem(AbstractMuseProblem):
     # explicitly below with its chain rule -- a blanket forward would hand variances to an engine that expects
     # log-variances.
     _FORWARDED = ("N", "ntheta", "model", "device", "get_zhat", "set_zhat", "close", "synchronize", "set_timing",
-                  "last_kernel_ms", "set_placement", "set_element_split")
+                  "last_kernel_ms", "set_placement", "set_element_split", "set_stencil", "get_stencil")
 
     def __getattr__(self, name):
         if name in PositiveThetaProblem._FORWARDED:

@@ -23,7 +23,12 @@ for b in blobs(sys.argv[1]):
     for line in txt.splitlines():
         m=re.match(r"^[0-9a-f]+ <(.+)>:$",line)
         if m: cur=m.group(1); res[cur]=hashlib.sha256(); continue
-        if cur and line.strip():
-            # strip addresses
-            res[cur].update(re.sub(r"^\s*[0-9a-f]+:\s*","",line).encode())
+        if cur and line.strip() and line.strip() != "...":   # ("...": zero padding up to the next kernel's alignment)
+            # strip addresses: the leading one, the one that opens the trailing `// address: encoding` comment (the encoding words
+            # stay in the hash) and the symbol offset of a branch target -- a kernel's place in its code object moves when another
+            # kernel joins the translation unit
+            line = re.sub(r"^\s*[0-9a-f]+:\s*", "", line)
+            line = re.sub(r"//\s*[0-9A-Fa-f]+:", "//", line)
+            line = re.sub(r"\s*<[^>]*>\s*$", "", line)
+            res[cur].update(line.encode())
 for k in sorted(res): print(k, res[k].hexdigest()[:16])
