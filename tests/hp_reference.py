@@ -147,8 +147,12 @@ def objective(model, x, z, theta):
 
 
 def score(model, x, z, theta):
-    """grad_theta logLike at (x, z, theta) and its per-component cond."""
-    x, z = np.asarray(x, np.float64).astype(LD), np.asarray(z, np.float64).astype(LD)
+    """grad_theta logLike at (x, z, theta) and its per-component cond.  x, z: fp64 arrays."""
+    return _score_ld(model, np.asarray(x, np.float64).astype(LD), np.asarray(z, np.float64).astype(LD), theta)
+
+
+def _score_ld(model, x, z, theta):
+    """score on longdouble x, z as they are (fd_value's exact MAP is not an fp64 vector)."""
     N = x.size
     k, iv, mu, B, n, _ = _coefs(model, N, theta)
     nL, sq = n.astype(LD), np.sqrt(n.astype(LD))
@@ -220,7 +224,10 @@ def _smooth_solve(iv, b):
 def exact_map(model, x, theta, z_start=None):
     """The MAP argmin_z f (longdouble): closed forms for the diagonal Gaussian models, a refined solve for smooth, and Newton
     steps from z_start (per element, longdouble) for cubic."""
-    x = np.asarray(x, np.float64).astype(LD)
+    return _exact_map_ld(model, np.asarray(x, np.float64).astype(LD), theta, z_start)
+
+
+def _exact_map_ld(model, x, theta, z_start=None):
     N = x.size
     _, iv, mu, _, _, _ = _coefs(model, N, theta)
     if model == "funnel":
@@ -304,3 +311,92 @@ def _cubic_polish(x, iv, z):
         g = iv * z - (x - h) * hp
         z = z - g / (iv + hp * hp - (x - h) * (LD(6) * z / LD(10)))
     return z
+
+
+# ------------------------------------------------------------------------------------------------ finite-difference get_H! values
+FD_MODELS = ("funnel", "noise", "smooth", "normal_mean_var", "offset_noise")
+
+
+def fd_value(model, N, seed, sim, theta0, j, eps):
+    """One value of get_H!'s finite-difference map (src/muse.jl:426-432) and what its bound needs: returns (f, aux) with
+
+        f(eps) = grad_theta logLike( x(theta0 + eps e_j; the simulation's normals), z*(x; theta0), theta0 )          (longdouble [ntheta])
+
+    x drawn at the perturbed theta from the normals of (seed, sim), z* the EXACT MAP at theta0 of that draw (closed form; the
+    refined solve for smooth), the score at theta0.  The perturbed component is the fp64 sum theta0[j] + eps -- the engine forms
+    that sum in fp64, so it is the input -- converted to longdouble afterwards; everything else is longdouble (x and z* are not
+    rounded to fp64 on the way).  Models: FD_MODELS, the Gaussian ones; offset_noise (models/offset_noise.h) draws and solves through
+    tests/pair_implicit_reference.py.  cubic is left with the oracle: the finite-difference entry returns no MAP to polish from, and
+    without one the cubic model has no exact MAP here (exact_map needs a z_start inside the right basin).
+
+    fd_bound(aux, atol) bounds |engine's value - f| per component for a unit whose record says status == 0 (g_converged).  It is
+    derived, not fitted, after points (b) and (c) of test_gpu_stencil.test_get_H_branches_against_the_dense_H:
+
+    1. The kernel stops on its own fp64 gradient, |g_fp64|_inf <= atol, and that is within gb = rounding(cond_g).max() of the true
+       gradient at its MAP zhat: |grad f(zhat)|_inf <= atol + gb.  (cond_g is evaluated at z*; at zhat it differs by O(dz) of it.)
+    2. f is quadratic in z with Hessian Hz, so zhat - z* = Hz^-1 grad f(zhat).  Diagonal models: per element
+       dz_i <= (atol + gb) / H_ii, H_ii = 1 + iv_i (diag_hessian).  smooth: |dz|_2 <= sqrt(N) (atol + gb) / lambda_min with
+       lambda_min >= e^{-max theta0} (A^T A is positive semi-definite).
+    3. Every score component is a quadratic in z, so its change over dz is bounded exactly.  With q_i the absolute value of the
+       quadratic's argument at z* (|z*_i| for funnel and smooth, |x_i - z*_i| for noise, |z*_i - mu_k| for normal_mean_var,
+       |x_i - z*_i - mu_k| for offset_noise) a component 1/2 (iv_k sum q^2 - n_k) moves by at most
+           iv_k (sum_i q_i dz_i + 1/2 sum_i dz_i^2)                 -- for smooth by Cauchy-Schwarz  iv_k (|q_k|_2 D + 1/2 D^2), D = |dz|_2,
+       and the pair models' linear component iv_k sum (+-)(argument) by at most iv_k sum_i dz_i.
+    4. The kernel's fp64 evaluation of the score at zhat is within rounding(cond_score) of the exact one, cond evaluated on
+       |z*| + dz (on |q_k|_2 + D for smooth), which covers zhat.
+    The bound is the sum of 3 and 4: no other slack, no constant from running a kernel.  (Not in it: the engine's draw differs from
+    the reference's by the generator's K_GEN 2^-52 max(1, r) per normal and one ulp of exp(theta/2), some 1e-7 of atol at the
+    atol = 1e-8 the tests use; a solve reports g_converged at |g|_inf <= atol, not within 1e-15 of it.)"""
+    assert model in FD_MODELS
+    th0 = np.atleast_1d(np.asarray(theta0, dtype=np.float64))
+    thp = th0.copy()
+    thp[j] = th0[j] + np.float64(eps)                  # the fp64 sum: the input
+    if model == "offset_noise":
+        import pair_implicit_reference as P
+        x, zt, _, _ = P.sample(model, N, seed, sim, thp)
+        zs = P.exact_map(model, x, zt, N, th0)
+        th = th0.astype(LD)
+        K = th.size // 2
+        k, n = blocks(N, K), block_sizes(N, K)
+        mu, iv = th[:K][k], np.exp(-th[K:])[k]
+        r = x - zs - mu
+        f = np.concatenate([_bsum(iv * r, k, K), LD(0.5) * (_bsum(iv * r * r, k, K) - n.astype(LD))])
+        q, qa = np.abs(r), np.abs(x) + np.abs(zs) + np.abs(mu)
+        gabs = np.abs(zs) + iv * qa                    # grad_z (1/2 o) = z - iv r on absolute values
+        hdiag = LD(1) + iv
+        pair = True
+    else:
+        x, _ = sample_x_z(model, N, seed, sim, thp)
+        zs = _exact_map_ld(model, x, th0)
+        f, _ = _score_ld(model, x, zs, th0)
+        k, iv, mu, K, n, _ = _coefs(model, N, th0)
+        gabs = objective(model, x, zs, th0)[3]
+        hdiag = None if model == "smooth" else iv + LD(1)
+        pair = model in PAIR_MODELS
+        if model == "noise":
+            q = qa = np.abs(x - zs)
+        elif pair:
+            q, qa = np.abs(zs - mu), np.abs(zs) + np.abs(mu)
+        else:
+            q = qa = np.abs(zs)
+    f64 = lambda v: np.asarray(v, dtype=np.float64)
+    aux = dict(model=model, N=N, K=K, k=k, n=f64(n), iv=f64(_bsum(iv, k, K)) / f64(n), q=f64(q), qa=f64(qa), gabs=f64(gabs),
+               hdiag=None if hdiag is None else f64(hdiag), pair=pair, lam_min=float(np.exp(-np.max(th0))), x=x, zs=zs)
+    return f, aux
+
+
+def fd_bound(aux, atol):
+    """|engine's fd value - fd_value's f| per component for a status == 0 unit: points 1-4 of fd_value's docstring."""
+    k, K, n, iv, q, qa = aux["k"], aux["K"], aux["n"], aux["iv"], aux["q"], aux["qa"]
+    ga = atol + float(rounding(aux["gabs"]).max())                    # 1.
+    bs = lambda v: np.bincount(k, weights=v, minlength=K)
+    if aux["model"] == "smooth":                                      # 2., 3. (Cauchy-Schwarz), 4. on |q_k|_2 + D
+        D = np.sqrt(aux["N"]) * ga / aux["lam_min"]
+        q2 = np.sqrt(bs(q * q))
+        return iv * (q2 * D + 0.5 * D * D) + rounding(0.5 * (iv * np.sqrt(n) * (q2 + D) ** 2 + n))
+    dz = ga / aux["hdiag"]                                            # 2.
+    quad = iv * (bs(q * dz) + 0.5 * bs(dz * dz)) + rounding(0.5 * (iv * np.sqrt(n) * bs((qa + dz) ** 2) + n))
+    if not aux["pair"]:
+        return quad
+    lin = iv * bs(dz) + rounding(iv * np.sqrt(n) * bs(qa + dz))
+    return np.concatenate([lin, quad])

@@ -1,6 +1,8 @@
 """The extended-precision reference (tests/hp_reference.py) validated before any GPU time is spent, and the CPU oracle held to it:
 Philox known answers, the oracle's normals within the committed generator bound K, the oracle's per-sim operators, MAPs and
 implicit H within the reference's stated bounds at the edge sizes."""
+import os
+
 import numpy as np
 import pytest
 
@@ -173,3 +175,96 @@ def test_oracle_implicit_H(O, model, N, theta):
     H, _ = O.implicit_H(model, N, 17, 2, theta, atol=1e-10, cg_maxiter=1000)
     Hh = R.implicit_H(model, N, 17, 2, theta).astype(np.float64)
     np.testing.assert_allclose(H, Hh, rtol=1e-6, atol=1e-6 * np.abs(Hh).max())
+
+
+# ------------------------------------------------------------------------------------------------ finite-difference get_H! values
+MODELS_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "museinference.jl_amd", "models")
+_FD_REFERENCE = {}      # (model, N, seed, sim, theta0, j, theta0[j] + eps) -> (f, aux): computed once, shared by the tests, never changed
+
+
+def fd_reference(model, N, seed, sim, theta0, j, eps):
+    th = np.atleast_1d(np.asarray(theta0, dtype=np.float64))
+    key = (model, N, seed, sim, th.tobytes(), j, float(th[j] + np.float64(eps)))
+    if key not in _FD_REFERENCE:
+        _FD_REFERENCE[key] = R.fd_value(model, N, seed, sim, th, j, eps)
+    return _FD_REFERENCE[key]
+
+
+def fd_mismatches(model, N, seed, sim_begin, lo, hi, theta0, offsets, per_unit, F, info, atol, ctx=""):
+    """Every entry of F [hi - lo, G, ntheta] (the units [lo, hi) of the list (sim_begin, column 0), (sim_begin, column 1), ...)
+    against hp_reference.fd_value within fd_bound: the entries outside it, each naming its unit, simulation, column, grid point,
+    offset and score component.  No unit is left out: every record must say status == 0, which is what the bound is derived for."""
+    theta0, offsets = np.atleast_1d(np.asarray(theta0, np.float64)), np.asarray(offsets, np.float64)
+    nth, G = theta0.size, offsets.shape[1]
+    assert F.shape == (hi - lo, G, nth) and info.shape == (hi - lo, G), (ctx, F.shape, info.shape)
+    assert np.all(info["status"] == 0), (ctx, "status", info["status"])
+    bad = []
+    for u in range(hi - lo):
+        sim, j = sim_begin + (lo + u) // nth, (lo + u) % nth
+        for g in range(G):
+            eps = offsets[u if per_unit else j, g]
+            f, aux = fd_reference(model, N, seed, sim, theta0, j, eps)
+            err, bound = np.abs(F[u, g] - f).astype(np.float64), R.fd_bound(aux, atol)
+            for i in np.nonzero(~(err <= bound))[0]:
+                bad.append(f"{ctx} unit {lo + u} sim {sim} column {j} grid {g} offset {eps:+.4g} component {i}: got {F[u, g, i]!r} "
+                           f"want {float(f[i])!r} err {err[i]:.3e} bound {bound[i]:.3e}")
+    return bad
+
+
+FD_CPU_CASES = [("funnel", 257, [0.4, -0.3, 0.9]), ("noise", 300, [-0.25]), ("smooth", 129, [-3.0, -2.93]),
+                ("normal_mean_var", 257, [0.3, -0.2, 0.5, -0.4]), ("offset_noise", 257, [0.3, -0.2, 0.5, -0.4])]
+
+
+def _fd_oracle(O, model):
+    """(context manager, the oracle's model name) for one of hp_reference.FD_MODELS."""
+    import contextlib
+    if model in ("normal_mean_var", "offset_noise"):
+        return O.user_model(os.path.join(MODELS_DIR, model + ".h"), model), "user"
+    return contextlib.nullcontext(), model
+
+
+@pytest.mark.parametrize("model,N,theta0", FD_CPU_CASES)
+def test_oracle_fd_values_within_the_derived_bound(O, model, N, theta0):
+    """The oracle's finite-difference values against hp_reference.fd_value within fd_bound (derived in fd_value's docstring), without
+    any kernel: both fiducial modes, offsets shared by the simulations and one row per unit, an offset of 0, a column range that
+    begins and ends inside a Jacobian -- and every record g_converged at atol = 1e-8, the condition of the GPU test."""
+    from oracle_problem import OracleBatchedProblem
+    nth, nsims, G, atol, seed, s0 = len(theta0), 3, 3, 1e-8, 9, 4
+    lo, hi = 1, nsims * nth - (1 if nth > 1 else 0)
+    rng = np.random.default_rng(N)
+    cm, name = _fd_oracle(O, model)
+    with cm:
+        orc = OracleBatchedProblem(None, name, nth, N=N, nthreads=1)
+        for fid_mode in (0, 1):
+            shared = rng.uniform(-0.05, 0.05, size=(nth, G))
+            shared[:, 1] = 0.0
+            F, info = orc.fd_values_columns(seed, s0, lo, hi, theta0, shared, atol=atol, fid_mode=fid_mode)
+            assert not fd_mismatches(model, N, seed, s0, lo, hi, theta0, shared, False, F, info, atol, f"shared fid_mode {fid_mode}")
+            per = rng.uniform(-0.05, 0.05, size=(hi - lo, G))
+            F, info = orc.fd_values_columns(seed, s0, lo, hi, theta0, per, per_unit=True, atol=atol, fid_mode=fid_mode)
+            assert not fd_mismatches(model, N, seed, s0, lo, hi, theta0, per, True, F, info, atol, f"per unit fid_mode {fid_mode}")
+
+
+@pytest.mark.parametrize("model,N,theta0", FD_CPU_CASES)
+def test_fd_bound_rejects_a_score_taken_at_the_perturbed_theta(O, model, N, theta0):
+    """The negative control: the same draw and the same MAP at theta0, but the score evaluated at theta0 + eps e_j -- a recipe that
+    two implementations can share.  The checker must refuse it (an offset of 0 aside, where the two recipes coincide)."""
+    nth, atol, seed, s0 = len(theta0), 1e-8, 9, 4
+    th = np.asarray(theta0, np.float64)
+    off = np.tile([0.03, 0.0, -0.02], (nth, 1))
+    cm, name = _fd_oracle(O, model)
+    F = np.empty((nth, 3, nth))
+    info = np.zeros((nth, 3), dtype=[("status", np.int32)])
+    with cm:
+        zfid = O.map_and_score_batch(name, N, seed, 2**40, 2**40 + 1, th, atol=atol, z0_mode=0)[1][0]
+        for j in range(nth):
+            for g in range(3):
+                t = th.copy()
+                t[j] = th[j] + off[j, g]
+                x, _ = O.sample_x_z(name, N, seed, s0, t)
+                zh, inf = O.zhat_at_theta(name, x, zfid, th, atol)
+                assert inf["status"] == 0
+                F[j, g] = O.grad_theta(name, x, zh, t)          # wrong on purpose: theta0 is what get_H! scores at
+    bad = fd_mismatches(model, N, seed, s0, 0, nth, th, off, False, F, info, atol)
+    assert bad and not [b for b in bad if " grid 1 " in b], bad
+    assert all(any(f" column {j} grid {g} " in b for b in bad) for j in range(nth) for g in (0, 2)), bad
