@@ -29,7 +29,8 @@
  *                      (src/simple.jl:59-73, docs/src/index.md:154-168).
  *   MUSE_MODEL_NOISE   z_i ~ N(0,1), x_i ~ N(z_i, e^theta); ntheta = 1.
  *   MUSE_MODEL_SMOOTH  z as FUNNEL, x = A z + n with A the periodic (1/4,1/2,1/4) stencil -- or, after muse_set_stencil, the
- *                      periodic symmetric 3-tap operator (A z)_i = w1 (z_{i-1} + z_{i+1}) + w0 z_i of the context's weights:
+ *                      periodic symmetric 3-tap operator (A z)_i = w1 (z_{i-1} + z_{i+1}) + w0 z_i of the context's weights,
+ *                      and, after muse_set_noise, with a noise sd per element and masked elements:
  *                      the one coupled latent model (a non-diagonal Hessian in z) of the HIP path.
  *   MUSE_MODEL_USER    a user-supplied elementwise model (the closures of SimpleMuseProblem as compiled code): three C
  *                      functions in a header (include/muse_model.h: the joint draw, d(-logLike)/dz with the objective's
@@ -149,6 +150,23 @@ int muse_set_stencil(muse_ctx* ctx, const double* w /* {w0, w1}, or NULL: the bu
 /* The operator in use: w_out[2] = {w0, w1} ({0.5, 0.25} for the built-in), *runtime_out = 1 when the weights were set (the launches
  * read them) and 0 for the built-in kernels; either pointer may be NULL.  MUSE_ERR_INVALID for another model. */
 int muse_get_stencil(muse_ctx* ctx, double* w_out, int* runtime_out);
+/* The noise of MUSE_MODEL_SMOOTH as context state: a standard deviation per element and a mask -- deconvolution and field inference
+ * with a noise level that changes from pixel to pixel and pixels that were not observed:
+ *     x_i = (A z)_i + s_i n2_i,   -logLike = 1/2 sum_i omega_i r_i^2 + 1/2 sum_i e^{-theta_k} z_i^2 + 1/2 sum_k n_k theta_k,   r = x - A z,
+ * s_i = sd[i] and omega_i = 1 / (sd[i] * sd[i]) (two rounded operations) where mask[i] == 1, both 0 where mask[i] == 0: a masked
+ * element's x enters nothing (the data vector may hold anything finite or not there) and a draw writes exactly 0 there.  A is the
+ * context's stencil, the built-in or muse_set_stencil's.  The score is unchanged (the block sums of z^2).  Once set, EVERY entry point
+ * that takes the context uses the noise (per-simulation operators, batched / multi / gathered maps, both get_H! branches,
+ * muse_run*): the vectors are device vectors of the context, every launch points at them and runs the kernels that read them.  Like
+ * muse_set_constants the call waits for the context's launches first.  With sd == 1 everywhere and no mask the results are those of
+ * the context without noise, bit for bit.
+ * sd == NULL: back to unit noise, every element observed, AND the kernels a context launches when this was never called.
+ * MUSE_ERR_INVALID: another model, a library built from a user's model header, an sd that is not finite or not > 0, a mask value
+ * other than 0 or 1, a mask that hides every element of some theta block -- the context keeps the noise it had. */
+int muse_set_noise(muse_ctx* ctx, const double* sd /* N, finite, > 0 */, const double* mask /* N of 0.0 / 1.0, or NULL: all observed */, int mem);
+/* The noise in use: sd_out[N] and mask_out[N] as they were set (all 1 without), *runtime_out = 1 when the launches read noise vectors
+ * and 0 for the kernels without; any pointer may be NULL.  MUSE_ERR_INVALID for another model. */
+int muse_get_noise(muse_ctx* ctx, double* sd_out, double* mask_out, int* runtime_out);
 /* The functions of a user-supplied model's header evaluated on the HOST for one element (include/muse_model.h) -- what the
  * reference gets from AD for free has to be checkable for hand-written derivatives (src/simple.jl:84-85): Python's
  * check_model_consistency differentiates these values numerically.  out[10] = { muse_model_grad's return value, the objective

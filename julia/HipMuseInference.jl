@@ -256,6 +256,19 @@ function get_stencil(prob::HipMuseProblem)
     check(ccall((:muse_get_stencil, libmuse_hip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cint}), prob.ctx, w, rt))
     (; weights=(w[1], w[2]), runtime=rt[] != 0)
 end
+# The noise of the "smooth" model as state of the problem (include/muse_hip.h: muse_set_noise): a standard deviation per element
+# (finite, > 0) and a mask (true / 1: observed, false / 0: masked; `nothing`: all observed) -- used by every operator, map and
+# get_H! branch from the next call on; sd = `nothing`: back to unit noise and the kernels without noise vectors.
+function set_noise(prob::HipMuseProblem, sd::Union{Nothing,Vector{Float64}}, mask::Union{Nothing,AbstractVector}=nothing)
+    sd === nothing && return check(ccall((:muse_set_noise, libmuse_hip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint), prob.ctx, C_NULL, C_NULL, MEM_HOST))
+    m = mask === nothing ? nothing : Float64.(mask)
+    check(ccall((:muse_set_noise, libmuse_hip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint), prob.ctx, sd, m === nothing ? C_NULL : m, MEM_HOST))
+end
+function get_noise(prob::HipMuseProblem)
+    sd = Vector{Float64}(undef, prob.N); mask = Vector{Float64}(undef, prob.N); rt = Ref{Cint}(0)
+    check(ccall((:muse_get_noise, libmuse_hip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}), prob.ctx, sd, mask, rt))
+    (; sd=sd, mask=mask .!= 0, runtime=rt[] != 0)
+end
 # plain maps over simulations the context has drawn before load their standard normals instead of generating them: off / on
 set_normals_cache(prob::HipMuseProblem, enabled::Bool) =
     check(ccall((:muse_set_normals_cache, libmuse_hip), Cint, (Ptr{Cvoid}, Cint), prob.ctx, enabled))

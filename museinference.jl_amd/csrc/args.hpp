@@ -165,6 +165,8 @@ struct BatchArgs {
     // LAST, kernarg segment only: the run-time constants of a user-supplied model (include/muse_model.h, muse_const) -- the
     // launching context's device vectors and their lengths.  Per LAUNCH (round 5; a process-wide __device__ symbol before:
     // a launch of another context of the same library still in flight would have read the new owner's pointers).
+    // ... or, in the library of the built-in models, consts[0 .. 1] = {omega, s}: the stencil model's noise vectors when they are
+    // context state (muse_set_noise; models.hpp, SmoothNoiseModel), [ld] each with the pad element 0
     const double* consts[4];
     union {
         long const_len[4];
@@ -309,16 +311,18 @@ struct LaunchShape {
                  // streaming placement (muse_engine.cpp, tier_big: the same bits, 2.4x faster than the small tiers' streaming passes)
     bool lds_s;  // stencil model in a cluster: the search direction in LDS (vec.hpp, LdsMirror)
     bool taps;   // stencil model: the operator's weights are the launch's (BatchArgs::taps), not the built-in literals
+    bool noise;  // stencil model: the launch carries the context's noise vectors (BatchArgs::consts[0 .. 1] = {omega, s}; models.hpp,
+                 // SmoothNoiseModel) and its weights -- (1/2, 1/4) when none were set -- in BatchArgs::taps
     size_t lds;
     void* done_event;  // hipEvent_t (or null) that the launch itself signals on completion: no separate event packet
 };
 hipError_t launch_solver(const LaunchShape& s, const BatchArgs& a, hipStream_t stream);
-// (taps: the stencil model with the launch's own weights, BatchArgs::taps)
-hipError_t launch_sample(int model, bool taps, const BatchArgs& a, uint64_t sim, double* x, double* z, double* noise, hipStream_t stream);
+// (taps: the stencil model with the launch's own weights, BatchArgs::taps; noisy: with its own noise vectors as well)
+hipError_t launch_sample(int model, bool taps, bool noisy, const BatchArgs& a, uint64_t sim, double* x, double* z, double* noise, hipStream_t stream);
 // the standard normals of ONE stream into a slot of the normals cache's layout ([2][ld]: n1, n2), drawn by the whole GPU instead of
 // by the one workgroup that solves the stream's problem (muse_engine.cpp, fd_values_impl: the fiducial MAP of get_H!)
 hipError_t launch_normals(uint64_t seed, uint64_t sim, int64_t ld, double* slot, hipStream_t stream);
-hipError_t launch_loglike(int model, bool taps, const BatchArgs& a, const double* x, const double* z, double* g, double* out, hipStream_t stream);
+hipError_t launch_loglike(int model, bool taps, bool noise, const BatchArgs& a, const double* x, const double* z, double* g, double* out, hipStream_t stream);
 // the device-resident loop: false where the placement has no loop kernel (cluster placements); max_grid = the number of
 // workgroups that are certainly resident at once (they meet at the end of every iteration)
 bool loop_supported(const LaunchShape& s);

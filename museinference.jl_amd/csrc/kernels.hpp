@@ -968,9 +968,11 @@ hipError_t loop_place(const LaunchShape& s, const LoopCall& c) {
 #define MUSE_PART_3(X) MUSE_INSTANTIATE_ELEMENTWISE(X, FunnelModel<kMaxTheta>)
 #define MUSE_PART_4(X) MUSE_INSTANTIATE_ELEMENTWISE(X, NoiseModel)
 #define MUSE_PART_5(X) MUSE_INSTANTIATE_STENCIL(X, SmoothModel<2>) MUSE_INSTANTIATE_STENCIL(X, SmoothModel<4>) \
-                       MUSE_INSTANTIATE_STENCIL(X, SmoothTapsModel<2>) MUSE_INSTANTIATE_STENCIL(X, SmoothTapsModel<4>)
+                       MUSE_INSTANTIATE_STENCIL(X, SmoothTapsModel<2>) MUSE_INSTANTIATE_STENCIL(X, SmoothTapsModel<4>) \
+                       MUSE_INSTANTIATE_STENCIL(X, SmoothNoiseModel<2>) MUSE_INSTANTIATE_STENCIL(X, SmoothNoiseModel<4>)
 #define MUSE_PART_6(X) MUSE_INSTANTIATE_STENCIL(X, SmoothModel<kMaxTheta>) MUSE_INSTANTIATE_BIG(X, SmoothModel<kBigTheta>) \
-                       MUSE_INSTANTIATE_STENCIL(X, SmoothTapsModel<kMaxTheta>) MUSE_INSTANTIATE_BIG(X, SmoothTapsModel<kBigTheta>)
+                       MUSE_INSTANTIATE_STENCIL(X, SmoothTapsModel<kMaxTheta>) MUSE_INSTANTIATE_BIG(X, SmoothTapsModel<kBigTheta>) \
+                       MUSE_INSTANTIATE_STENCIL(X, SmoothNoiseModel<kMaxTheta>) MUSE_INSTANTIATE_BIG(X, SmoothNoiseModel<kBigTheta>)
 #define MUSE_PART_7(X) MUSE_INSTANTIATE_BIG(X, FunnelModel<kBigTheta>)
 #endif
 constexpr int kKernelParts = 8;

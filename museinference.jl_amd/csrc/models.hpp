@@ -66,6 +66,7 @@ struct SmoothModel {  // z as funnel, x = A z + n, A = periodic (1/4, 1/2, 1/4);
     using SCoef = double; using GCoef = double;
     static constexpr bool kStencil = true;
     static constexpr int kId = MUSE_MODEL_SMOOTH;
+    static constexpr bool kNoise = false;   // unit noise variance, every element observed
     __device__ static __forceinline__ double w0() { return 0.5; }
     __device__ static __forceinline__ double w1() { return 0.25; }
     __device__ static __forceinline__ double score_term(double, double z, int) { return z * z; }
@@ -82,9 +83,74 @@ struct SmoothTapsModel {
     using SCoef = double; using GCoef = double;
     static constexpr bool kStencil = true;
     static constexpr int kId = MUSE_MODEL_SMOOTH;
+    static constexpr bool kNoise = false;
     __device__ static __forceinline__ double w0() { return ((kernarg_f64)__builtin_amdgcn_kernarg_segment_ptr())[offsetof(BatchArgs, taps) / 8]; }
     __device__ static __forceinline__ double w1() { return ((kernarg_f64)__builtin_amdgcn_kernarg_segment_ptr())[offsetof(BatchArgs, taps) / 8 + 1]; }
     __device__ static __forceinline__ double score_term(double, double z, int) { return z * z; }
+};
+// ... and with the noise as context state too (muse_set_noise): x_i = (A z)_i + s_i n2_i, -logLike = 1/2 sum_i omega_i r_i^2 + ...,
+// omega_i = 1 / sd_i^2 and s_i = sd_i where the element is observed, both 0 where it is masked.  The two vectors ([ld], the pad
+// element 0) are the launching context's; their pointers travel in the kernarg-only tail of the argument block, in the first two
+// slots of BatchArgs::consts, which the library of the built-in models does not use otherwise (a launch that carries no noise
+// carries the weights (1/2, 1/4) of the built-in stencil in BatchArgs::taps: the engine's set_launch_constants).  omega enters
+// every expression through noise_weigh below; at omega = s = 1 these kernels give SmoothTapsModel's bits.
+typedef __attribute__((address_space(4))) const int64_t* kernarg_i64;
+template <int MAXB_>
+struct SmoothNoiseModel : SmoothTapsModel<MAXB_> {
+    static constexpr bool kNoise = true;
+    // k = 0: omega, k = 1: s
+    __device__ static __forceinline__ const double* noise_ptr(int k) {
+        return (const double*)((kernarg_i64)__builtin_amdgcn_kernarg_segment_ptr())[offsetof(BatchArgs, consts) / 8 + k];
+    }
+    __device__ static __forceinline__ int64_t noise_ld() { return ((kernarg_i64)__builtin_amdgcn_kernarg_segment_ptr())[offsetof(BatchArgs, ld) / 8]; }
+};
+template <class Model>
+constexpr bool noise_model() {
+    if constexpr (Model::kStencil) return Model::kNoise;
+    else return false;
+}
+// rho = omega r, the weighted residual of a stencil model with run-time noise -- and r itself for every other model, whose
+// code therefore does not change: gradient t - stencil_apply(rho_m, rho_0, rho_p), objective share fma(t, z0, fma(rho0, r0, facc))
+template <class Model>
+__device__ __forceinline__ double noise_weigh(double omega, double r) {
+    if constexpr (noise_model<Model>()) return omega * r;
+    else return r;
+}
+// ... and the residual itself as the expressions above may see it: r where the element is observed, 0 where it is masked
+// (omega = 0), whatever the data vector holds there.  r = x - (A z) of a masked element is formed from an x that the model never
+// reads -- NaN and inf are the usual fill of masked pixels -- and 0 * NaN is NaN, so the product alone would not drop it: the
+// select does, before noise_weigh and before the objective's fma(rho0, r0, .).  Where omega != 0 it returns r unchanged, so
+// at omega = 1 the bits are SmoothTapsModel's; for every other model it is r.
+template <class Model>
+__device__ __forceinline__ double noise_residual(double omega, double r) {
+    if constexpr (noise_model<Model>()) return omega != 0.0 ? r : 0.0;
+    else return r;
+}
+// One of the two noise vectors as a pass reads it (K = 0: omega, K = 1: s): a range-checked descriptor over the context's vector,
+// made from the kernel-argument segment where the pass begins (scalar work, nothing held across the kernel).  Read-only inside a
+// launch, so neighbours' elements need no coherent loads.  For the models without run-time noise: no state, the value 1.
+template <class Model, int K, bool ON = noise_model<Model>()>
+struct NoiseVec {
+    __device__ __forceinline__ double get1(int) const { return 1.0; }
+    __device__ __forceinline__ void own_pair(int, double& a, double& b) const { a = 1.0; b = 1.0; }
+    __device__ __forceinline__ double get(int, int) const { return 1.0; }
+};
+template <class Model, int K>
+struct NoiseVec<Model, K, true> {
+    rsrc_t rsrc;
+    mutable double c1;
+    __device__ __forceinline__ NoiseVec() : rsrc(make_rsrc(Model::noise_ptr(K), Model::noise_ld() * 8)) {}
+    __device__ __forceinline__ double get1(int i) const { return load_f64(rsrc, i); }
+    __device__ __forceinline__ void own_pair(int i0, double& a, double& b) const { load_f64x2(rsrc, i0, a, b); }
+    // element loop (vec.hpp, for_elems): the thread's pair with one 16-byte load at the even element, its second half at the odd one
+    __device__ __forceinline__ double get(int jj, int i) const {
+        if ((jj & 1) == 0) {
+            double d0;
+            load_f64x2(rsrc, i, d0, c1);
+            return d0;
+        }
+        return c1;
+    }
 };
 // (A z)_i of a stencil model from the element and its two neighbours: w1 (zl + zr) + w0 z0, the product rounded, then ONE fma
 // (stencil_fma: from the neighbours' sum, for a caller that loads the centre element behind it)

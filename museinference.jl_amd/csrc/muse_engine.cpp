@@ -113,6 +113,12 @@ struct muse_ctx {
     // or -- never set, or set back with NULL -- the built-in (1/4, 1/2, 1/4) and its kernels
     bool stencil_taps = false;
     double stencil_w[kStencilWeights] = {0.5, 0.25};
+    // the stencil model's noise (muse_set_noise): omega_i = 1 / sd_i^2 and s_i = sd_i where the element is observed, 0 where it is
+    // masked, as device vectors [ld] (pad element 0) that every launch points at and that select the kernels that read them; the
+    // host copies are what muse_get_noise hands back.  Never set, or set back with NULL: unit noise and the kernels without it
+    bool noise_on = false;
+    double* noise_dev[2] = {nullptr, nullptr};   // {omega, s}
+    std::vector<double> noise_sd, noise_mask;
     bool nc_auto = true;                 // muse_set_normals_cache: plain maps may store / load the normals of repeated simulations
     double* fid_norm = nullptr;          // [2][ld]: the standard normals of get_H!'s fiducial stream, drawn by a kernel of its own (fd_values_impl)
     unsigned int* fid_flag = nullptr;    // device word: the tag of the last fiducial MAP published inside a finite-difference launch
@@ -435,6 +441,7 @@ static int launch_batch(muse_ctx* c, BatchArgs& a, hipEvent_t done = nullptr) {
         shape.big = tier_big(c, pl, a.nmaps);
         shape.lds_s = !implicit && pl == P_C256 && stencil_lds_s(c, a.csize);
         shape.taps = c->stencil_taps;
+        shape.noise = c->noise_on;
         shape.done_event = done;
         const hipError_t e = launch_solver(shape, a, c->lane->stream);
         if (e != hipSuccess) rc = fail(MUSE_ERR_HIP, std::string("solver launch: ") + hipGetErrorString(e));
@@ -530,8 +537,10 @@ static void set_launch_constants(const muse_ctx* c, BatchArgs& a) {
         a.consts[k] = c->consts_dev[k];
         a.const_len[k] = c->consts_len[k];
     }
-    if (c->stencil_taps)   // (the stencil model has no constants: the weights take the place of their lengths, args.hpp)
+    if (c->stencil_taps || c->noise_on)   // (the stencil model has no constants: the weights take the place of their lengths, args.hpp)
         for (int k = 0; k < kStencilWeights; ++k) a.taps[k] = c->stencil_w[k];
+    if (c->noise_on)       // (... and the noise vectors the place of the first two pointers; the kernels with run-time noise read the
+        for (int k = 0; k < 2; ++k) a.consts[k] = c->noise_dev[k];   // weights too: (1/2, 1/4), the built-in's bits, when none were set)
 }
 
 extern "C" {
@@ -706,6 +715,7 @@ int muse_ctx_destroy(muse_ctx* c) {
         for (int k = 0; k < MUSE_MODEL_MAX_CONST; ++k) { muse_host_consts[k] = nullptr; muse_host_const_len[k] = 0; }
     }
 #endif
+    hipFree(c->noise_dev[0]); hipFree(c->noise_dev[1]);
     hipFree(c->x_data); hipFree(c->fid_flag); hipFree(c->fid_norm); hipFree(c->tmp);
     hipFree(c->small_dev); if (c->tsample_dev) hipFree(c->tsample_dev); if (c->tsample_pin) hipHostFree(c->tsample_pin);
     if (c->comm_buf) hipFree(c->comm_buf);
@@ -839,6 +849,84 @@ int muse_get_stencil(muse_ctx* c, double* w_out, int* runtime_out) {
     if (w_out)
         for (int k = 0; k < kStencilWeights; ++k) w_out[k] = c->stencil_w[k];
     if (runtime_out) *runtime_out = c->stencil_taps ? 1 : 0;
+    return MUSE_OK;
+}
+int muse_set_noise(muse_ctx* c, const double* sd, const double* mask, int mem) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+#ifdef MUSE_USER_MODEL_HEADER
+    (void)sd; (void)mask; (void)mem;
+    return fail(MUSE_ERR_INVALID, "muse_set_noise: this library was built from a user's model header and holds no stencil model");
+#else
+    if (c->model != MUSE_MODEL_SMOOTH) return fail(MUSE_ERR_INVALID, "muse_set_noise: the context's model is not MUSE_MODEL_SMOOTH");
+    if (mem != MUSE_MEM_HOST && mem != MUSE_MEM_DEVICE) return fail(MUSE_ERR_INVALID, "muse_set_noise: mem must be MUSE_MEM_HOST or MUSE_MEM_DEVICE");
+    if (!sd) {   // back to unit noise, every element observed, and the kernels without noise vectors
+        rc = muse_synchronize(c);
+        if (rc) return rc;
+        c->noise_on = false;
+        c->noise_sd.clear();
+        c->noise_mask.clear();
+        return MUSE_OK;
+    }
+    const size_t n = (size_t)c->N;
+    std::vector<double> hsd(n), hmask(n, 1.0);
+    if (mem == MUSE_MEM_DEVICE) {
+        HIPCHK(hipMemcpy(hsd.data(), sd, n * sizeof(double), hipMemcpyDeviceToHost));
+        if (mask) HIPCHK(hipMemcpy(hmask.data(), mask, n * sizeof(double), hipMemcpyDeviceToHost));
+    } else {
+        memcpy(hsd.data(), sd, n * sizeof(double));
+        if (mask) memcpy(hmask.data(), mask, n * sizeof(double));
+    }
+    // (every check before anything of the context changes: a refused call leaves it as it was)
+    for (size_t i = 0; i < n; ++i) {
+        if (!isfinite(hsd[i]) || !(hsd[i] > 0.0)) return fail(MUSE_ERR_INVALID, "muse_set_noise: every sd must be finite and > 0");
+        if (hmask[i] != 0.0 && hmask[i] != 1.0) return fail(MUSE_ERR_INVALID, "muse_set_noise: a mask value is 0 (masked) or 1 (observed)");
+    }
+    for (int k = 0; k < c->ntheta; ++k) {
+        bool seen = false;
+        for (int64_t i = c->bnd[k]; i < c->bnd[k + 1] && !seen; ++i) seen = hmask[(size_t)i] != 0.0;
+        if (!seen) return fail(MUSE_ERR_INVALID, "muse_set_noise: the mask hides every element of a theta block");
+    }
+    rc = muse_synchronize(c);   // nothing in flight reads the vectors that are about to be replaced
+    if (rc) return rc;
+    std::vector<double> hw((size_t)c->ld, 0.0), hs((size_t)c->ld, 0.0);   // (the pad element: 0 in both)
+    for (size_t i = 0; i < n; ++i) {
+        if (hmask[i] == 0.0) continue;
+        const double var = hsd[i] * hsd[i];   // omega = 1 / (sd sd): two rounded operations
+        hw[i] = 1.0 / var;
+        hs[i] = hsd[i];
+    }
+    // (staged: fresh device vectors, filled, and only then put in the place of the context's -- a failed allocation or copy
+    //  leaves the vectors the kernels read, and what muse_get_noise reports of them, as they were)
+    double* fresh[2] = {nullptr, nullptr};
+    const double* host[2] = {hw.data(), hs.data()};
+    for (int k = 0; k < 2; ++k) {
+        hipError_t e = hipMalloc(&fresh[k], (size_t)c->ld * sizeof(double));
+        if (e == hipSuccess) e = hipMemcpy(fresh[k], host[k], (size_t)c->ld * sizeof(double), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            hipFree(fresh[0]); hipFree(fresh[1]);
+            return fail(MUSE_ERR_HIP, std::string("muse_set_noise: the noise vectors: ") + hipGetErrorString(e));
+        }
+    }
+    for (int k = 0; k < 2; ++k) {
+        hipFree(c->noise_dev[k]);
+        c->noise_dev[k] = fresh[k];
+    }
+    c->noise_sd.swap(hsd);
+    c->noise_mask.swap(hmask);
+    c->noise_on = true;
+    return MUSE_OK;
+#endif
+}
+int muse_get_noise(muse_ctx* c, double* sd_out, double* mask_out, int* runtime_out) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (c->model != MUSE_MODEL_SMOOTH) return fail(MUSE_ERR_INVALID, "muse_get_noise: the context's model is not MUSE_MODEL_SMOOTH");
+    for (int64_t i = 0; i < c->N; ++i) {
+        if (sd_out) sd_out[i] = c->noise_on ? c->noise_sd[(size_t)i] : 1.0;
+        if (mask_out) mask_out[i] = c->noise_on ? c->noise_mask[(size_t)i] : 1.0;
+    }
+    if (runtime_out) *runtime_out = c->noise_on ? 1 : 0;
     return MUSE_OK;
 }
 int muse_set_constants(muse_ctx* c, int k, const double* values, int64_t count, int mem) {
@@ -1071,7 +1159,7 @@ int muse_sample_x_z(muse_ctx* c, uint64_t seed, int64_t sim, const double* theta
     base_args(c, a, theta);
     a.seed = seed;
     double *dx = c->tmp, *dz = c->tmp + c->ld, *dn = c->tmp + 2 * c->ld;
-    HIPCHK(launch_sample(c->model, c->stencil_taps, a, (uint64_t)sim, dx, dz, dn, c->lane->stream));
+    HIPCHK(launch_sample(c->model, c->stencil_taps, c->noise_on, a, (uint64_t)sim, dx, dz, dn, c->lane->stream));
     if (x_out) HIPCHK(hipMemcpyAsync(x_out, dx, (size_t)c->N * sizeof(double), out_kind(mem), c->lane->stream));
     if (z_out) HIPCHK(hipMemcpyAsync(z_out, dz, (size_t)c->N * sizeof(double), out_kind(mem), c->lane->stream));
     HIPCHK(hipStreamSynchronize(c->lane->stream));
@@ -1084,7 +1172,7 @@ static int run_loglike(muse_ctx* c, const double* x, const double* z, const doub
     double *dx = c->tmp, *dz = c->tmp + c->ld;
     HIPCHK(hipMemcpyAsync(dx, x, (size_t)c->N * sizeof(double), in_kind(mem), c->lane->stream));
     HIPCHK(hipMemcpyAsync(dz, z, (size_t)c->N * sizeof(double), in_kind(mem), c->lane->stream));
-    HIPCHK(launch_loglike(c->model, c->stencil_taps, a, dx, dz, gdev, c->small_dev, c->lane->stream));
+    HIPCHK(launch_loglike(c->model, c->stencil_taps, c->noise_on, a, dx, dz, gdev, c->small_dev, c->lane->stream));
     return MUSE_OK;
 }
 
@@ -1493,7 +1581,7 @@ static bool loop_usable(muse_ctx* c, int S, int64_t nlocal, LaunchShape* shape_o
     const int64_t nprob_total = (int64_t)S + 1;
     const int pl = choose_place(c);
     LaunchShape shape;
-    shape.model = c->model; shape.ntheta = nt; shape.place = pl; shape.grid = 0; shape.implicit = false; shape.lds_s = false; shape.taps = false;
+    shape.model = c->model; shape.ntheta = nt; shape.place = pl; shape.grid = 0; shape.implicit = false; shape.lds_s = false; shape.taps = false; shape.noise = false;
     shape.big = false;  // (the loop kernel runs the resident placements)
     shape.done_event = nullptr;
     const bool xg_lds = pl == P_R512x10;

@@ -120,6 +120,20 @@ __global__ void __launch_bounds__(256) smooth_finish_taps_kernel(BatchArgs a, co
     }
 }
 
+// (... and its own noise, muse_set_noise: x = A z + s n2 with ONE rounding behind the stencil, as the solver's sampler pass forms it,
+//  and exactly 0 where the element is masked, s = 0; the vectors are the launch's, BatchArgs::consts[0 .. 1] = {omega, s})
+__global__ void __launch_bounds__(256) smooth_finish_noise_kernel(BatchArgs a, const double* __restrict__ z, const double* __restrict__ noise,
+                                                                  double* __restrict__ x) {
+    const int64_t N = a.N;
+    const double* __restrict__ sn = a.consts[1];
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t im = i == 0 ? N - 1 : i - 1, ip = i == N - 1 ? 0 : i + 1;
+        const double si = sn[i];
+        const double xv = fma(si, noise[i], stencil_apply<SmoothNoiseModel<kMaxTheta>>(z[im], z[i], z[ip]));
+        x[i] = si != 0.0 ? xv : 0.0;
+    }
+}
+
 // logLike and grad_z logLike (note the sign: the solver works with -logLike), plus the per-block score
 // sums; one workgroup, fixed-shape reduction (same element->thread map as the solver).
 template <class Model>
@@ -165,8 +179,18 @@ __global__ void __launch_bounds__(1024) loglike_kernel(BatchArgs a, const double
             const double r0 = xin[ic] - stencil_apply<Model>(zm1, z0, zp1);
             const double rp = xin[ip1] - stencil_apply<Model>(z0, zp1, zp2);
             const double t = ivk * z0;
+            if constexpr (noise_model<Model>()) {   // (run-time noise: the weighted residuals, models.hpp, noise_weigh)
+                const double* __restrict__ om = a.consts[0];
+                // (a masked element's x may hold anything, NaN included: its residual is dropped before it is weighed)
+                const double om_m = om[im1], om_0 = om[ic], om_p = om[ip1];
+                const double mm = noise_residual<Model>(om_m, rm), m0 = noise_residual<Model>(om_0, r0), mp = noise_residual<Model>(om_p, rp);
+                const double qm = noise_weigh<Model>(om_m, mm), q0 = noise_weigh<Model>(om_0, m0), qp = noise_weigh<Model>(om_p, mp);
+                sum[0] = valid ? fma(t, z0, fma(q0, m0, sum[0])) : sum[0];
+                gi = valid ? t - stencil_apply<Model>(qm, q0, qp) : 0.0;
+            } else {
             sum[0] = valid ? fma(t, z0, fma(r0, r0, sum[0])) : sum[0];
             gi = valid ? t - stencil_apply<Model>(rm, r0, rp) : 0.0;
+            }
         } else {
             gi = Model::grad(ivk, xin[i], zin[i], sum[0], i);
         }
@@ -255,6 +279,8 @@ hipError_t launch_solver(const LaunchShape& s, const BatchArgs& a, hipStream_t s
     if (s.big) {  // the big tier (args.hpp, BigTheta; muse_engine.cpp, tier_big): streaming placements only
         if (s.model == MUSE_MODEL_FUNNEL)
             return s.implicit ? launch_place_implicit<FunnelModel<kBigTheta>>(s, a, st) : launch_place_big<FunnelModel<kBigTheta>>(s, a, st);
+        if (s.model == MUSE_MODEL_SMOOTH && s.noise)
+            return s.implicit ? launch_place_implicit<SmoothNoiseModel<kBigTheta>>(s, a, st) : launch_place_big<SmoothNoiseModel<kBigTheta>>(s, a, st);
         if (s.model == MUSE_MODEL_SMOOTH && s.taps)
             return s.implicit ? launch_place_implicit<SmoothTapsModel<kBigTheta>>(s, a, st) : launch_place_big<SmoothTapsModel<kBigTheta>>(s, a, st);
         if (s.model == MUSE_MODEL_SMOOTH)
@@ -268,6 +294,10 @@ hipError_t launch_solver(const LaunchShape& s, const BatchArgs& a, hipStream_t s
                    : nt == 2 ? launch_place_implicit<FunnelModel<2>>(s, a, st)
                    : nt <= 4 ? launch_place_implicit<FunnelModel<4>>(s, a, st)
                              : launch_place_implicit<FunnelModel<kMaxTheta>>(s, a, st);
+        if (s.noise)
+            return nt <= 2   ? launch_place_implicit<SmoothNoiseModel<2>>(s, a, st)
+                   : nt <= 4 ? launch_place_implicit<SmoothNoiseModel<4>>(s, a, st)
+                             : launch_place_implicit<SmoothNoiseModel<kMaxTheta>>(s, a, st);
         if (s.taps)
             return nt <= 2   ? launch_place_implicit<SmoothTapsModel<2>>(s, a, st)
                    : nt <= 4 ? launch_place_implicit<SmoothTapsModel<4>>(s, a, st)
@@ -282,6 +312,10 @@ hipError_t launch_solver(const LaunchShape& s, const BatchArgs& a, hipStream_t s
                : nt == 2 ? launch_place<FunnelModel<2>>(s, a, st)
                : nt <= 4 ? launch_place<FunnelModel<4>>(s, a, st)
                          : launch_place<FunnelModel<kMaxTheta>>(s, a, st);
+    if (s.noise)
+        return nt <= 2   ? launch_place<SmoothNoiseModel<2>>(s, a, st)
+               : nt <= 4 ? launch_place<SmoothNoiseModel<4>>(s, a, st)
+                         : launch_place<SmoothNoiseModel<kMaxTheta>>(s, a, st);
     if (s.taps)
         return nt <= 2   ? launch_place<SmoothTapsModel<2>>(s, a, st)
                : nt <= 4 ? launch_place<SmoothTapsModel<4>>(s, a, st)
@@ -407,11 +441,11 @@ hipError_t launch_normals(uint64_t seed, uint64_t sim, int64_t ld, double* slot,
     return hipGetLastError();
 }
 
-hipError_t launch_sample(int model, bool taps, const BatchArgs& a, uint64_t sim, double* x, double* z, double* noise, hipStream_t st) {
+hipError_t launch_sample(int model, bool taps, bool noisy, const BatchArgs& a, uint64_t sim, double* x, double* z, double* noise, hipStream_t st) {
     const int grid = (int)((a.N + 255) / 256 < 4096 ? (a.N + 255) / 256 : 4096);
 #ifdef MUSE_USER_MODEL_HEADER
     (void)noise;
-    if (model != MUSE_MODEL_USER || taps) return hipErrorInvalidValue;
+    if (model != MUSE_MODEL_USER || taps || noisy) return hipErrorInvalidValue;
     hipLaunchKernelGGL(sample_user_kernel, dim3(grid), dim3(256), 0, st, a, sim, x, z);
     return hipGetLastError();
 #endif
@@ -419,15 +453,16 @@ hipError_t launch_sample(int model, bool taps, const BatchArgs& a, uint64_t sim,
     else if (model == MUSE_MODEL_FUNNEL) hipLaunchKernelGGL(sample_kernel<MUSE_MODEL_FUNNEL>, dim3(grid), dim3(256), 0, st, a, sim, x, z);
     else {
         hipLaunchKernelGGL(sample_kernel<MUSE_MODEL_SMOOTH>, dim3(grid), dim3(256), 0, st, a, sim, noise, z);
-        if (taps) hipLaunchKernelGGL(smooth_finish_taps_kernel, dim3(grid), dim3(256), 0, st, a, z, noise, x);
+        if (noisy) hipLaunchKernelGGL(smooth_finish_noise_kernel, dim3(grid), dim3(256), 0, st, a, z, noise, x);
+        else if (taps) hipLaunchKernelGGL(smooth_finish_taps_kernel, dim3(grid), dim3(256), 0, st, a, z, noise, x);
         else hipLaunchKernelGGL(smooth_finish_kernel, dim3(grid), dim3(256), 0, st, a.N, z, noise, x);
     }
     return hipGetLastError();
 }
 
-hipError_t launch_loglike(int model, bool taps, const BatchArgs& a, const double* x, const double* z, double* g, double* out, hipStream_t st) {
+hipError_t launch_loglike(int model, bool taps, bool noise, const BatchArgs& a, const double* x, const double* z, double* g, double* out, hipStream_t st) {
 #ifdef MUSE_USER_MODEL_HEADER
-    if (model != MUSE_MODEL_USER || taps) return hipErrorInvalidValue;
+    if (model != MUSE_MODEL_USER || taps || noise) return hipErrorInvalidValue;
 #ifdef MUSE_MODEL_PAIR
     if (a.ntheta > kMaxTheta) return hipErrorInvalidValue;
 #else
@@ -440,6 +475,8 @@ hipError_t launch_loglike(int model, bool taps, const BatchArgs& a, const double
     if (model == MUSE_MODEL_NOISE) hipLaunchKernelGGL(loglike_kernel<NoiseModel>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
     else if (model == MUSE_MODEL_FUNNEL && a.ntheta > kMaxTheta) hipLaunchKernelGGL(loglike_kernel<FunnelModel<kBigTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
     else if (model == MUSE_MODEL_FUNNEL) hipLaunchKernelGGL(loglike_kernel<FunnelModel<kMaxTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
+    else if (noise && a.ntheta > kMaxTheta) hipLaunchKernelGGL(loglike_kernel<SmoothNoiseModel<kBigTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
+    else if (noise) hipLaunchKernelGGL(loglike_kernel<SmoothNoiseModel<kMaxTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
     else if (taps && a.ntheta > kMaxTheta) hipLaunchKernelGGL(loglike_kernel<SmoothTapsModel<kBigTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
     else if (taps) hipLaunchKernelGGL(loglike_kernel<SmoothTapsModel<kMaxTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
     else if (a.ntheta > kMaxTheta) hipLaunchKernelGGL(loglike_kernel<SmoothModel<kBigTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);

@@ -384,6 +384,28 @@ struct Solver : PairState<Model::kPair> {
         r_out = r0;
         return t - stencil_apply<Model>(rm, r0, rp);
     }
+    // (run-time noise, models.hpp: the same with the residuals weighed, q = omega r -- gradient t - A (omega r), the element's share
+    //  fma(t, z0, fma(q0, r0, .)); a function of its own so that the one above, and every kernel made from it, stays as it was)
+    template <class ZT, class OM>
+    __device__ __forceinline__ double stencil_grad_weighed(ZT&& zt, const OM& om, int i, double& t_out, double& z_out, double& r_out,
+                                                           double& q_out) const {
+        const int N = (int)a.N;
+        auto wrap = [&](int k) { return k < 0 ? k + N : (k >= N ? k - N : k); };
+        const int im2 = wrap(i - 2), im1 = wrap(i - 1), ip1 = wrap(i + 1), ip2 = wrap(i + 2);
+        const double zm2 = zt(im2), zm1 = zt(im1), z0 = zt(i), zp1 = zt(ip1), zp2 = zt(ip2);
+        const double om_m = om.get1(im1), om_0 = om.get1(i), om_p = om.get1(ip1);
+        // (a masked element's x may hold anything, NaN included: its residual is dropped before it is weighed, models.hpp)
+        const double rm = noise_residual<Model>(om_m, x.get1(im1) - stencil_apply<Model>(zm2, zm1, z0));
+        const double r0 = noise_residual<Model>(om_0, x.get1(i) - stencil_apply<Model>(zm1, z0, zp1));
+        const double rp = noise_residual<Model>(om_p, x.get1(ip1) - stencil_apply<Model>(z0, zp1, zp2));
+        const double qm = noise_weigh<Model>(om_m, rm), q0 = noise_weigh<Model>(om_0, r0), qp = noise_weigh<Model>(om_p, rp);
+        const double t = this->ivk(0, i) * z0;
+        t_out = t;
+        z_out = z0;
+        r_out = r0;
+        q_out = q0;
+        return t - stencil_apply<Model>(qm, q0, qp);
+    }
 
     // ---- stencil model, pair-wise --------------------------------------------------------------
     // A lane loads its own element pair of z, s, x with one 16-byte buffer instruction each and gets the
@@ -424,9 +446,11 @@ struct Solver : PairState<Model::kPair> {
             if constexpr (USE_S) v = fma(c, s.get1(k), v);
             return v;
         };
+        const NoiseVec<Model, 0> om;   // (run-time noise: omega at i0-1 .. i0+2 travels like x -- own pair, wave shifts, edge loads)
 #pragma unroll 1
         for (int ic = 2 * t; ic < n; ic += 2 * U * pstride) {
             double g0[U], g1[U], tt[U][2], zz[U][2], rr[U][2];
+            double qq[noise_model<Model>() ? U : 1][2];   // (the weighted residuals: run-time noise only)
             Pair spv[U];
             bool interior[U];
 #pragma unroll
@@ -440,6 +464,12 @@ struct Solver : PairState<Model::kPair> {
                 const int ix = edge ? (lane == 0 ? i0 - 1 : i0 + 2) : kOutOfRange;
                 Pair ze = load_edge(z.rsrc, ie);
                 const double xe = x.get1(ix);
+                Pair wp{1.0, 1.0};
+                double we = 1.0;
+                if constexpr (noise_model<Model>()) {
+                    om.own_pair(i0, wp.a, wp.b);
+                    we = om.get1(ix);
+                }
                 Pair sp{0.0, 0.0}, ztp = zp;
                 if constexpr (USE_S) {
                     s.own_pair(i0, sp.a, sp.b);
@@ -459,10 +489,33 @@ struct Solver : PairState<Model::kPair> {
                 const double r1 = xp.b - stencil_apply<Model>(ztp.a, ztp.b, ztR.a);  // r at i0+1
                 const double r2 = xR - stencil_apply<Model>(ztp.b, ztR.a, ztR.b);    // r at i0+2
                 const double t0 = ivk(0, i0) * ztp.a, t1 = ivk(1, i0 + 1) * ztp.b;
-                g0[u] = t0 - stencil_apply<Model>(rm, r0, r1);
-                g1[u] = t1 - stencil_apply<Model>(r0, r1, r2);
+                // The run-time-noise forks of this loop (here, in the patch loop and at facc below) repeat the lines of their else
+                // branches with rho = noise_weigh(omega, r) in r's place instead of calling the helper in ONE shared line: the
+                // else branches are the text every kernel without noise was compiled from, and leaving them untouched is what
+                // keeps those kernels' disassembly -- their code hashes -- as they were.  An edit to the gradient or to the
+                // objective's share goes into BOTH branches of each fork, and into stencil_grad / stencil_grad_weighed.
+                if constexpr (noise_model<Model>()) {
+                    double wL = dpp_move<kDppWaveShr1>(wp.b), wR = dpp_move<kDppWaveShl1>(wp.a);
+                    if (lane == 0) wL = we;
+                    if (lane == 63) wR = we;
+                    // (a masked element's x may hold anything, NaN included: its residual is dropped before it is weighed)
+                    const double mm = noise_residual<Model>(wL, rm), m0 = noise_residual<Model>(wp.a, r0);
+                    const double m1 = noise_residual<Model>(wp.b, r1), m2 = noise_residual<Model>(wR, r2);
+                    const double qm = noise_weigh<Model>(wL, mm), q0 = noise_weigh<Model>(wp.a, m0);
+                    const double q1 = noise_weigh<Model>(wp.b, m1), q2 = noise_weigh<Model>(wR, m2);
+                    g0[u] = t0 - stencil_apply<Model>(qm, q0, q1);
+                    g1[u] = t1 - stencil_apply<Model>(q0, q1, q2);
+                    qq[u][0] = q0; qq[u][1] = q1;
+                } else {
+                    g0[u] = t0 - stencil_apply<Model>(rm, r0, r1);
+                    g1[u] = t1 - stencil_apply<Model>(r0, r1, r2);
+                }
                 tt[u][0] = t0; zz[u][0] = ztp.a; rr[u][0] = r0;
                 tt[u][1] = t1; zz[u][1] = ztp.b; rr[u][1] = r1;
+                if constexpr (noise_model<Model>()) {   // (... and it is the dropped residual that meets rho in the objective's share)
+                    rr[u][0] = noise_residual<Model>(wp.a, r0);
+                    rr[u][1] = noise_residual<Model>(wp.b, r1);
+                }
             }
             // wrap-around, pad and out-of-range pairs: element-wise with modular neighbour indices
 #pragma unroll
@@ -473,7 +526,13 @@ struct Solver : PairState<Model::kPair> {
                     for (int v = 0; v < 2; ++v) {
                         const int i = i0 + v;
                         double gt = 0.0, t_ = 0.0, z_ = 0.0, r_ = 0.0;
-                        if (i < N) gt = stencil_grad(ztf, i, t_, z_, r_);
+                        if constexpr (noise_model<Model>()) {
+                            double q_ = 0.0;
+                            if (i < N) gt = stencil_grad_weighed(ztf, om, i, t_, z_, r_, q_);
+                            qq[u][v] = q_;
+                        } else {
+                            if (i < N) gt = stencil_grad(ztf, i, t_, z_, r_);
+                        }
                         (v == 0 ? g0[u] : g1[u]) = gt;
                         tt[u][v] = t_; zz[u][v] = z_; rr[u][v] = r_;
                     }
@@ -482,8 +541,13 @@ struct Solver : PairState<Model::kPair> {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int i0 = ic + 2 * u * pstride;
-                facc = fma(tt[u][0], zz[u][0], fma(rr[u][0], rr[u][0], facc));
-                facc = fma(tt[u][1], zz[u][1], fma(rr[u][1], rr[u][1], facc));
+                if constexpr (noise_model<Model>()) {
+                    facc = fma(tt[u][0], zz[u][0], fma(qq[u][0], rr[u][0], facc));
+                    facc = fma(tt[u][1], zz[u][1], fma(qq[u][1], rr[u][1], facc));
+                } else {
+                    facc = fma(tt[u][0], zz[u][0], fma(rr[u][0], rr[u][0], facc));
+                    facc = fma(tt[u][1], zz[u][1], fma(rr[u][1], rr[u][1], facc));
+                }
                 body(u, i0, g0[u], g1[u], spv[u].a, spv[u].b);
             }
             (written.template flush<U>(ic, pstride), ...);
@@ -1599,14 +1663,21 @@ struct Solver : PairState<Model::kPair> {
             }
             if constexpr (Model::kStencil) {
                 pass_barrier();
+                const NoiseVec<Model, 1> sn;   // (run-time noise: x = A z + s n2, and 0 where the element is masked, s = 0)
                 for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
                     const bool valid = i < N;
                     const int ic = valid ? i : 0;
                     const int im = ic == 0 ? (int)N - 1 : ic - 1, ip = ic == (int)N - 1 ? 0 : ic + 1;
                     const double zl = g.get1(im), zr = g.get1(ip);
                     const double az = stencil_apply<Model>(zl, g.get1(ic), zr);
-                    const double xv = az + x.get(jj, i);
-                    x.set(jj, i, valid ? xv : 0.0);
+                    if constexpr (noise_model<Model>()) {
+                        const double si = sn.get(jj, i);
+                        const double xv = fma(si, x.get(jj, i), az);
+                        x.set(jj, i, valid && si != 0.0 ? xv : 0.0);
+                    } else {
+                        const double xv = az + x.get(jj, i);
+                        x.set(jj, i, valid ? xv : 0.0);
+                    }
                 }, x);
             }
         } else {
@@ -2165,6 +2236,7 @@ struct Solver : PairState<Model::kPair> {
             const double a0 = stencil_fma<Model>(lr, w.get1(ic));
             return valid ? a0 : 0.0;
         };
+        const NoiseVec<Model, 0> om;   // (run-time noise: the Hessian is A' Omega A + diag(e^-theta), the right-hand side A' Omega A (z/2)|_k)
         // imp_split == ntheta: this element is ONE column of one simulation's H (few simulations, many theta: the
         // columns spread over the GPU, each repeating the cheap atol = 1e-1 MAP); imp_split == 1: all columns
         const int split = a.imp_split > 1 ? a.imp_split : 1;
@@ -2180,7 +2252,7 @@ struct Solver : PairState<Model::kPair> {
                     t1.set(jj, i, blk(jj, i) == j ? 0.5 * zt : 0.0);
                 }, t1);
                 pass_barrier();
-                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) { t2.set(jj, i, Aat(t1, i)); }, t2);
+                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) { t2.set(jj, i, noise_weigh<Model>(om.get(jj, i), Aat(t1, i))); }, t2);
                 pass_barrier();
                 for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
                     const double bi = Aat(t2, i);
@@ -2217,7 +2289,7 @@ struct Solver : PairState<Model::kPair> {
                 // ---- Ap = A_hess p, p.Ap -----------------------------------------------------------
                 double s1[1] = {0.0};
                 if constexpr (Model::kStencil) {
-                    for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) { t1.set(jj, i, Aat(pp, i)); }, t1);
+                    for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) { t1.set(jj, i, noise_weigh<Model>(om.get(jj, i), Aat(pp, i))); }, t1);
                     pass_barrier();
                     for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
                         const double pi = pp.get(jj, i);

@@ -147,6 +147,14 @@ class ShardedMuseProblem:
     def get_stencil(self):
         return self.local.get_stencil()
 
+    def set_noise(self, noise_sd, mask=None):
+        """The "smooth" model's noise standard deviations and mask (HipMuseProblem.set_noise) on this rank's problem: every rank calls
+        it with the same vectors -- they are state of the rank's own context, nothing is exchanged."""
+        return self.local.set_noise(noise_sd, mask)
+
+    def get_noise(self):
+        return self.local.get_noise()
+
     # -- the muse! outer loop in the library's native code, sharded (muse_run_sharded of the C ABI): with the engine's own
     #    communicator every rank runs the loop itself -- one gathered map per iteration, the same step on every rank --
     #    and no Python, torch tensor or allocation sits between two maps.  Without it muse_() drives the maps from Python.

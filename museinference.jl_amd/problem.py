@@ -185,8 +185,11 @@ class HipMuseProblem(AbstractMuseProblem):
     supports_native_muse = True  # muse_() may hand the whole outer loop to muse_run (class attribute: wrappers
                                  # that forward attribute access to a HipMuseProblem do not inherit it)
 
-    def __init__(self, x, model="funnel", ntheta=1, prior=None, device=0, N=None, constants=None, stencil=None):
-        """stencil: (w0, w1) -- model="smooth" only -- the weights of the operator (A z)_i = w1 (z_{i-1} + z_{i+1}) + w0 z_i in place
+    def __init__(self, x, model="funnel", ntheta=1, prior=None, device=0, N=None, constants=None, stencil=None, noise_sd=None, mask=None):
+        """noise_sd, mask: -- model="smooth" only -- a noise standard deviation per element (N finite doubles > 0; a scalar is
+        broadcast) and which elements were observed (N of True / False, None: all): x_i = (A z)_i + sd_i n_i, masked elements enter
+        nothing; set_noise changes them later.
+        stencil: (w0, w1) -- model="smooth" only -- the weights of the operator (A z)_i = w1 (z_{i-1} + z_{i+1}) + w0 z_i in place
         of the built-in (1/2, 1/4); set_stencil changes them later.
         constants: {"P": array of N doubles, ...} for a user model written with run-time constants
         (ElementwiseModel.from_source(..., runtime_constants=["P", ...]); include/muse_model.h, muse_const) -- what the
@@ -218,6 +221,8 @@ class HipMuseProblem(AbstractMuseProblem):
                 self.set_constants(name, values)
             if stencil is not None:
                 self.set_stencil(stencil)
+            if noise_sd is not None or mask is not None:
+                self.set_noise(np.ones(self.N) if noise_sd is None else noise_sd, mask)
         except Exception:
             self.close()        # (a refused option: the context that was just created does not outlive the error)
             raise
@@ -239,6 +244,27 @@ class HipMuseProblem(AbstractMuseProblem):
             return
         w = _capi.f8(weights, 2)
         self._check(self._lib.muse_set_stencil(self._ctx, _capi.ptr(w)))
+
+    def set_noise(self, noise_sd, mask=None):
+        """The noise of the "smooth" model as context state (muse_set_noise): noise_sd = N standard deviations, finite and > 0 (a
+        scalar is broadcast), mask = N of True / 1 (observed) and False / 0 (masked), or None: all observed.  x_i = (A z)_i +
+        sd_i n_i; -logLike weighs the residual r_i^2 with 1 / sd_i^2 and leaves masked elements out; a draw writes 0 where masked.
+        Every operator, map, get_H! branch and muse() of this problem uses it from the next call on.  noise_sd = None: back to unit
+        noise and the kernels without noise vectors; all ones and no mask give those kernels' results bit for bit."""
+        if noise_sd is None:
+            self._check(self._lib.muse_set_noise(self._ctx, None, None, _capi.MEM_HOST))
+            return
+        sd = np.asarray(noise_sd, dtype=np.float64)
+        sd = _capi.f8(np.full(self.N, float(sd)) if sd.ndim == 0 else sd, self.N)
+        m = None if mask is None else _capi.f8(np.asarray(mask, dtype=np.float64), self.N)
+        self._check(self._lib.muse_set_noise(self._ctx, _capi.ptr(sd), None if m is None else _capi.ptr(m), _capi.MEM_HOST))
+
+    def get_noise(self):
+        """(noise_sd, mask, runtime): the N standard deviations and the N booleans (True: observed) as they were set -- all ones / all
+        True without -- and whether the launches read noise vectors (False: the kernels without run)."""
+        sd, m, rt = np.empty(self.N), np.empty(self.N), C.c_int()
+        self._check(self._lib.muse_get_noise(self._ctx, _capi.ptr(sd), _capi.ptr(m), C.byref(rt)))
+        return sd, m != 0.0, bool(rt.value)
 
     def get_stencil(self):
         """((w0, w1), runtime): the operator's weights and whether they were set (False: the built-in stencil's kernels run)."""
@@ -759,7 +785,8 @@ class PositiveThetaProblem(AbstractMuseProblem):
     # explicitly below with its chain rule -- a blanket forward would hand variances to an engine that expects
     # log-variances.
     _FORWARDED = ("N", "ntheta", "model", "device", "get_zhat", "set_zhat", "close", "synchronize", "set_timing",
-                  "last_kernel_ms", "set_placement", "set_element_split", "set_stencil", "get_stencil")
+                  "last_kernel_ms", "set_placement", "set_element_split", "set_stencil", "get_stencil",
+                  "set_noise", "get_noise")
 
     def __getattr__(self, name):
         if name in PositiveThetaProblem._FORWARDED:

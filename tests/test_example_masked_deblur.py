@@ -1,0 +1,16 @@
+"""examples/masked_deblur.py (the stencil model with a run-time noise map and a mask), run as a user would run it."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.gpu
+def test_masked_deblur_example_runs(gpu):
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "examples", "masked_deblur.py")], capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+    assert "theta[0]" in p.stdout and "theta[1]" in p.stdout and "exact posterior" in p.stdout
+    print(p.stdout)
