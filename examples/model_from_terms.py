@@ -35,6 +35,13 @@ result = M.muse(prob, np.zeros(2), nsims=200, rng=0, grad_z_logLike_atol=1e-6, t
 M.get_J_(result, prob, grad_z_logLike_atol=1e-6)
 M.get_H_(result, prob, nsims=20, implicit_diff=True)          # through the generated second derivatives
 H_implicit = result.H.copy()
+cg_default = np.array(result.metadata.pop("implicit_diff_cg_hists"))
+result.Hs, result.H = [], None
+# the Hessian in z is diagonal for an elementwise model: CG preconditioned by that diagonal ends after one iteration per column
+M.get_H_(result, prob, nsims=20, implicit_diff=True, implicit_diff_cg_kwargs={"Pl": "jacobi"})
+cg_jacobi = np.array(result.metadata.pop("implicit_diff_cg_hists"))
+print("CG iterations per column, default:", cg_default.min(), "to", cg_default.max(), "  with Pl = \"jacobi\":", cg_jacobi.min(), "to", cg_jacobi.max())
+np.testing.assert_allclose(result.H, H_implicit, rtol=1e-6, atol=1e-6 * np.abs(H_implicit).max())
 result.Hs, result.H = [], None
 M.get_H_(result, prob, nsims=20)                               # the finite-difference branch, same simulations
 sigma = np.sqrt(np.diag(result.Sigma))

@@ -379,9 +379,23 @@ int muse_implicit_H_columns(muse_ctx* ctx, uint64_t seed, int64_t sim_begin, int
  * |r| <= max(cg_reltol |b|, cg_abstol) or after cg_maxiter iterations (implicit_diff_cg_kwargs, splatted into IterativeSolvers.cg:
  * src/muse.jl:381; cg_maxiter = 0 leaves H = H1), and bit MUSE_IMPLICIT_H1_IS_ZERO of `flags` is implicit_diff_H1_is_zero
  * (src/muse.jl:353: the H1 sums are skipped, H1 = 0).  muse_implicit_H_batch / _columns ARE these entries with cg_reltol = sqrt(eps),
- * cg_abstol = 0, flags = 0 -- the same bits.  Values other than those are honoured by the kernels of the two-parameter family
- * (MUSE_MODEL_PAIR_SECOND); every other library refuses them with MUSE_ERR_INVALID: its kernels run the defaults. */
+ * cg_abstol = 0, flags = 0 -- the same bits, from the same kernels.  Values other than those are honoured by the kernels of the
+ * two-parameter family (MUSE_MODEL_PAIR_SECOND) and, through instantiations of their own, by those of a header of the one-parameter
+ * family (MUSE_MODEL_SECOND) and -- together with MUSE_IMPLICIT_PL_JACOBI below -- by those of the built-in funnel and noise models.  The
+ * built-in library without that bit, and the stencil model (smooth) always, refuse them with MUSE_ERR_INVALID: those kernels run the
+ * defaults.
+ *
+ * Bit MUSE_IMPLICIT_PL_JACOBI of `flags` is the keyword Pl of IterativeSolvers.cg with Pl = Diagonal(diag(A)), A the Hessian the branch
+ * applies (the diagonal is formed in the kernel from the model's own second derivative).  The recurrence is that of the package's
+ * preconditioned iterable: from x = 0, r = b, u = 0, rho = 1 an iteration is
+ *   c = Pl \ r;  rho' = rho, rho = c.r, beta = rho / rho';  u = c + beta u;  c = A u;  alpha = rho / (u.c);  x += alpha u;  r -= alpha c
+ * and it stops at |r|_2 <= max(cg_reltol |b|_2, cg_abstol) -- the true residual, not the preconditioned one -- or after cg_maxiter
+ * iterations; cg_iters_out counts these iterations.  For the elementwise models A is its own diagonal, so one iteration solves every
+ * column (0 for a column whose right-hand side is zero).  Refused with MUSE_ERR_INVALID and the reason in muse_last_error() by a
+ * library that cannot honour it: for the stencil model the Hessian's conditioning is the operator's, which no diagonal improves; a
+ * user's header whose preconditioned kernel would keep more than 256 bytes of scratch per lane is refused too. */
 #define MUSE_IMPLICIT_H1_IS_ZERO 1
+#define MUSE_IMPLICIT_PL_JACOBI 2
 int muse_implicit_H_batch_ex(muse_ctx* ctx, uint64_t seed, int64_t sim_begin, int64_t sim_end, const double* theta0, double atol,
                              int cg_maxiter, double cg_reltol, double cg_abstol, int flags, double* Hs_out, int32_t* cg_iters_out);
 int muse_implicit_H_columns_ex(muse_ctx* ctx, uint64_t seed, int64_t sim_begin, int64_t col_begin, int64_t col_end,

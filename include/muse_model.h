@@ -74,6 +74,10 @@
  * (the funnel: ozz = 1 + iv, ozx = -1, bz = 2 z, bx = 0, dx/dsd = n1).  Without MUSE_MODEL_SECOND the implicit entries refuse
  * the model and get_H! runs by finite differences (muse_fd_*: model-agnostic).  muse_model_eval of muse_hip.h evaluates the
  * header's functions on the host for one element -- what check_model_consistency differentiates numerically.
+ * With MUSE_IMPLICIT_PL_JACOBI (muse_hip.h; of both families) CG is preconditioned by that diagonal, c_i = r_i / (-ozz_i): one
+ * iteration solves a column.  That relies on ozz having ONE sign over the run (A negative definite: ozz > 0 at every MAP, as CG
+ * itself does).  The kernel treats ozz_i = 0 as a phantom slot -- the pad element and the slots behind the vector are such -- so a
+ * header that says ozz = 0 on a real element gets c_i = 0 there, not inf: that component of the solve is then simply never updated.
  *
  * TWO PARAMETERS PER BLOCK (round 6: location-type parameters).  In the family above a block has ONE parameter, the log-variance
  * of one Gaussian factor, and the engine knows how it enters: through exp(theta/2) in the draw, exp(-theta) in the objective,

@@ -300,24 +300,31 @@ function implicit_H_columns(prob::HipMuseProblem, seed::Integer, sim_begin, col_
     cols, its
 end
 # The same two with the remaining keywords of the reference's branch (cg_reltol, cg_abstol: IterativeSolvers.cg's keywords; H1_is_zero: get_H!'s implicit_diff_H1_is_zero -- values other than the
-#  defaults are honoured for headers of the two-parameter family and refused for every other model)
+#  defaults are honoured for a user's header with second derivatives and, together with Pl = :jacobi, for the built-in funnel and noise models; refused otherwise).  Pl = :jacobi is IterativeSolvers.cg's Pl as
+#  Diagonal(diag(A)) of the Hessian the branch applies, formed in the kernel (flag bit MUSE_IMPLICIT_PL_JACOBI); nothing: the identity
+const MUSE_IMPLICIT_H1_IS_ZERO = 1
+const MUSE_IMPLICIT_PL_JACOBI = 2
+function implicit_flags(H1_is_zero, Pl)
+    Pl === nothing || Pl === :jacobi || Pl == "jacobi" || throw(ArgumentError("Pl must be nothing (the identity) or :jacobi"))
+    (H1_is_zero ? MUSE_IMPLICIT_H1_IS_ZERO : 0) | (Pl === nothing ? 0 : MUSE_IMPLICIT_PL_JACOBI)
+end
 function implicit_H_batch_ex(prob::HipMuseProblem, seed::Integer, sims::UnitRange, θ₀; atol=1e-1, cg_maxiter=100, cg_reltol=sqrt(eps()),
-                          cg_abstol=0.0, H1_is_zero=false)
+                          cg_abstol=0.0, H1_is_zero=false, Pl=nothing)
     n = length(sims)
     Hs = Array{Float64}(undef, prob.nθ, prob.nθ, n); its = Matrix{Int32}(undef, prob.nθ, n)
     check(ccall((:muse_implicit_H_batch_ex, libmuse_hip), Cint,
                 (Ptr{Cvoid}, UInt64, Int64, Int64, Ptr{Float64}, Float64, Cint, Float64, Float64, Cint, Ptr{Float64}, Ptr{Int32}),
                 prob.ctx, UInt64(seed), first(sims), last(sims) + 1, standardizeθ(prob, θ₀), atol, cg_maxiter, cg_reltol, cg_abstol,
-                H1_is_zero ? 1 : 0, Hs, its))
+                implicit_flags(H1_is_zero, Pl), Hs, its))
     [permutedims(Hs[:, :, s]) for s in 1:n], its          # (the C ABI is row-major [sim][i][j])
 end
 function implicit_H_columns_ex(prob::HipMuseProblem, seed::Integer, sim_begin, col_begin, col_end, θ₀; atol=1e-1, cg_maxiter=100,
-                            cg_reltol=sqrt(eps()), cg_abstol=0.0, H1_is_zero=false)
+                            cg_reltol=sqrt(eps()), cg_abstol=0.0, H1_is_zero=false, Pl=nothing)
     cols = Matrix{Float64}(undef, prob.nθ, col_end - col_begin); its = Vector{Int32}(undef, col_end - col_begin)
     check(ccall((:muse_implicit_H_columns_ex, libmuse_hip), Cint,
                 (Ptr{Cvoid}, UInt64, Int64, Int64, Int64, Ptr{Float64}, Float64, Cint, Float64, Float64, Cint, Ptr{Float64}, Ptr{Int32}),
                 prob.ctx, UInt64(seed), sim_begin, col_begin, col_end, standardizeθ(prob, θ₀), atol, cg_maxiter, cg_reltol, cg_abstol,
-                H1_is_zero ? 1 : 0, cols, its))
+                implicit_flags(H1_is_zero, Pl), cols, its))
     cols, its
 end
 # The second derivatives of a header of the two-parameter family (MUSE_MODEL_PAIR_SECOND) for one element on the host:

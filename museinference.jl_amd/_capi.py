@@ -15,6 +15,7 @@ MODELS = {"funnel": MODEL_FUNNEL, "noise": MODEL_NOISE, "smooth": MODEL_SMOOTH} 
 MEM_HOST, MEM_DEVICE = 0, 1
 Z0_ZERO, Z0_TRUE, Z0_WARM = 0, 1, 2
 IMPLICIT_H1_IS_ZERO = 1   # muse_implicit_H_*_ex, flags (MUSE_IMPLICIT_H1_IS_ZERO)
+IMPLICIT_PL_JACOBI = 2    # ... (MUSE_IMPLICIT_PL_JACOBI): CG preconditioned by the Hessian's diagonal
 MAX_THETA = 8
 MAX_MAPS = 8
 UNIQUE_ID_BYTES = 128

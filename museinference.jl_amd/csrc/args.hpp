@@ -93,8 +93,9 @@ struct BatchArgs {
     int ntheta, kind;
     int64_t bnd[kMaxTheta + 1];  // block k = elements [bnd[k], bnd[k+1])
     int bnd32[kMaxTheta + 1];    // the same, 32-bit (N < 2^28), for the per-element block lookup
-    int imp_flags;    // BATCH_IMPLICIT: bit 0 = H1 is zero (src/muse.jl:353): its sums are skipped.  Read by the kernels of the
-                      // two-parameter family only (the other implicit kernels run IterativeSolvers.cg's defaults; was padding)
+    int imp_flags;    // BATCH_IMPLICIT: bit 0 = H1 is zero (src/muse.jl:353): its sums are skipped; bit 1 = Pl is the Hessian's diagonal
+                      // (MUSE_IMPLICIT_PL_JACOBI).  Read by the kernels of the two-parameter family and by the preconditioned ones
+                      // (the other implicit kernels run IterativeSolvers.cg's defaults; was padding)
     uint64_t seed;
     double atol;
     int nproblems, include_data, z0_mode, store_zhat;
@@ -154,10 +155,10 @@ struct BatchArgs {
     unsigned int fid_tag;
     union {
         int64_t fid_sim;           // BATCH_FD
-        double cg_abstol;          // BATCH_IMPLICIT (two-parameter family): CG stops at |r| <= max(cg_reltol |b|, cg_abstol)
+        double cg_abstol;          // BATCH_IMPLICIT (two-parameter family, preconditioned kernels): CG stops at |r| <= max(cg_reltol |b|, cg_abstol)
     };
     unsigned int* fid_flag;
-    double cg_reltol;              // BATCH_IMPLICIT (two-parameter family; was padding)
+    double cg_reltol;              // BATCH_IMPLICIT (two-parameter family, preconditioned kernels; was padding)
     union {  // read from the kernarg segment only (never copied to LDS)
         alignas(16) MapTheta maps[kMaxMaps];  // theta of every map, nmaps > 1
         BigTheta big;                         // ntheta > kMaxTheta
@@ -307,6 +308,8 @@ struct LoopArgs {
 struct LaunchShape {
     int model, ntheta, place, grid;
     bool implicit;
+    bool jacobi;  // implicit: the kernels with the preconditioned CG loop and the run-time CG keywords (MUSE_IMPLICIT_PL_JACOBI, or
+                  // any keyword the default kernels do not read); elementwise models only
     bool big;    // the big tier's instantiation (BigTheta): ntheta > kMaxTheta, or 2..kMaxTheta components of an elementwise model in a
                  // streaming placement (muse_engine.cpp, tier_big: the same bits, 2.4x faster than the small tiers' streaming passes)
     bool lds_s;  // stencil model in a cluster: the search direction in LDS (vec.hpp, LdsMirror)

@@ -36,9 +36,22 @@ __device__ __forceinline__ void load_problem_theta(const BatchArgs& a, double* a
     }
 }
 
+// The implicit-differentiation H with the preconditioned CG loop and every CG keyword at run time (MUSE_IMPLICIT_PL_JACOBI; solver.hpp,
+// run_implicit<true>) is a compile-time variant beside IMPLICIT with kernels of its own.  The flag rides on the placement type: a
+// third parameter of the kernel would rename every kernel of the library, and a body shared between two entry points changed the
+// instruction schedule of the existing ones (compared by tools/code_hash.py) -- this way they stay what they were, name and code.
+template <class P>
+struct JacobiPlace : P {};
+template <class P>
+struct place_is_jacobi : std::false_type {};
+template <class P>
+struct place_is_jacobi<JacobiPlace<P>> : std::true_type {};
+
 template <class Model, class Place, bool IMPLICIT = false>
 __global__ void __launch_bounds__(Place::T) __attribute__((amdgpu_waves_per_eu(Place::kWavesPerEu)))
 map_score_kernel(const BatchArgs /*read via the kernarg segment*/) {
+    constexpr bool JACOBI = place_is_jacobi<Place>::value;   // (elementwise models only: launch_place_implicit)
+    static_assert(!JACOBI || (IMPLICIT && !Model::kStencil), "the preconditioned loop is the implicit branch's, for the elementwise models");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int T = Place::T;
     // LDS carve (all offsets multiples of 16 B): reduction scratch, L-BFGS scalars, ticket, args, x, g
@@ -117,8 +130,8 @@ map_score_kernel(const BatchArgs /*read via the kernarg segment*/) {
             sv.parity = 0;
             wg_barrier<!Model::kStencil>();
             load_problem_theta<!Model::kStencil>(a, args_lds, p, tid);
-            if constexpr (IMPLICIT && Model::kPair) sv.run_implicit_pair(p, cl_scratch, lds_x, lds_g);
-            else if constexpr (IMPLICIT) sv.run_implicit(p, cl_scratch, lds_x, lds_g);
+            if constexpr (IMPLICIT && Model::kPair) sv.template run_implicit_pair<JACOBI>(p, cl_scratch, lds_x, lds_g);
+            else if constexpr (IMPLICIT) sv.template run_implicit<JACOBI>(p, cl_scratch, lds_x, lds_g);
             else sv.run(p, cl_scratch, lds_x, lds_g);
         }
 #ifdef MUSE_STAMPS
@@ -154,8 +167,8 @@ map_score_kernel(const BatchArgs /*read via the kernarg segment*/) {
                 Solver<Model, Place> sv(a, tid, red, shs);
                 sv.pk[0] = pk0;
                 sv.pk[1] = pk1;
-                if constexpr (IMPLICIT && Model::kPair) sv.run_implicit_pair(p, wg_scratch, lds_x, lds_g);
-                else if constexpr (IMPLICIT) sv.run_implicit(p, wg_scratch, lds_x, lds_g);
+                if constexpr (IMPLICIT && Model::kPair) sv.template run_implicit_pair<JACOBI>(p, wg_scratch, lds_x, lds_g);
+                else if constexpr (IMPLICIT) sv.template run_implicit<JACOBI>(p, wg_scratch, lds_x, lds_g);
                 else sv.run(p, wg_scratch, lds_x, lds_g);
             }
             // (raw barriers for the elementwise models: the MAP's stores keep draining while the next problem starts)
@@ -795,6 +808,7 @@ muse_loop_kernel(const BatchArgs /*read via the kernarg segment*/, const LoopArg
 // Launch shims.
 // ================================================================================================
 constexpr int kMaxDevices = 64;  // devices of one process (HIP device ordinals)
+constexpr int kJacobiScratchLimit = 256;  // bytes per lane (tools/regs.py, LIBRARY_SCRATCH_LIMIT): a preconditioned kernel beyond it is refused
 template <class Model, class Place, bool IMPLICIT = false>
 static hipError_t launch_one(const LaunchShape& s, const BatchArgs& a, hipStream_t stream) {
     auto kern = map_score_kernel<Model, Place, IMPLICIT>;
@@ -806,6 +820,18 @@ static hipError_t launch_one(const LaunchShape& s, const BatchArgs& a, hipStream
         const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds);
         if (e != hipSuccess) return e;
         lds_allowed[dev] = s.lds;
+    }
+    if constexpr (place_is_jacobi<Place>::value) {
+        // a user's header whose preconditioned kernel keeps its state in scratch (a heavy two-parameter model) is refused, with the
+        // reason (muse_engine.cpp, launch_batch), instead of running slower than the loop it replaces: looked at once per device
+        static int scratch_seen[kMaxDevices];   // 0: not yet, 1: within the bound, 2: beyond it
+        if (!scratch_seen[dev]) {
+            hipFuncAttributes at;
+            const hipError_t e = hipFuncGetAttributes(&at, (const void*)kern);
+            if (e != hipSuccess) return e;
+            scratch_seen[dev] = at.localSizeBytes > (size_t)kJacobiScratchLimit ? 2 : 1;
+        }
+        if (scratch_seen[dev] == 2) return hipErrorNotSupported;
     }
     // The completion event of a result area rides on the dispatch itself (its completion signal) instead of following
     // it as a packet of its own, which the next launch would have to wait behind.
@@ -853,6 +879,14 @@ hipError_t launch_place_big(const LaunchShape& s, const BatchArgs& a, hipStream_
 template <class Model>
 hipError_t launch_place_implicit(const LaunchShape& s, const BatchArgs& a, hipStream_t st) {
     constexpr int U = Model::kStencil ? kStencilU : kStreamU;
+    if (s.jacobi) {   // the preconditioned loop and the run-time CG keywords: kernels of their own, elementwise models only
+        if constexpr (!Model::kStencil) {
+            if (s.place == P_C256) return launch_one<Model, JacobiPlace<PlaceStreaming<256, true, U>>, true>(s, a, st);
+            return launch_one<Model, JacobiPlace<PlaceStreaming<512, false, U>>, true>(s, a, st);
+        } else {
+            return hipErrorInvalidValue;  // (muse_engine.cpp refuses the call before it gets here)
+        }
+    }
     if (s.place == P_C256) return launch_one<Model, PlaceStreaming<256, true, U, Model::kStencil>, true>(s, a, st);
     return launch_one<Model, PlaceStreaming<512, false, U>, true>(s, a, st);
 }

@@ -361,7 +361,8 @@ static void attach_ncache(BatchArgs& a, double* cache, int64_t sim0, int64_t cou
 
 // Fill the common fields and launch the solver for `a.nproblems` elements.  `done`: an event the launch itself signals when it
 // completes (NULL: none) -- a launch that returns MUSE_OK carries it.
-static int launch_batch(muse_ctx* c, BatchArgs& a, hipEvent_t done = nullptr) {
+// `jacobi`: an implicit batch that runs the kernels with the preconditioned CG loop and the run-time CG keywords (implicit_impl).
+static int launch_batch(muse_ctx* c, BatchArgs& a, hipEvent_t done = nullptr, bool jacobi = false) {
     common_args(c, a, a.nproblems);
     a.clock_out = c->prof_on ? c->clock_pin : nullptr;  // roofline leg only
     const bool implicit = a.kind == BATCH_IMPLICIT;
@@ -438,13 +439,18 @@ static int launch_batch(muse_ctx* c, BatchArgs& a, hipEvent_t done = nullptr) {
     {
         LaunchShape shape;
         shape.model = c->model; shape.ntheta = c->ntheta; shape.place = pl; shape.grid = grid; shape.implicit = implicit; shape.lds = lds;
+        shape.jacobi = implicit && jacobi;
         shape.big = tier_big(c, pl, a.nmaps);
         shape.lds_s = !implicit && pl == P_C256 && stencil_lds_s(c, a.csize);
         shape.taps = c->stencil_taps;
         shape.noise = c->noise_on;
         shape.done_event = done;
         const hipError_t e = launch_solver(shape, a, c->lane->stream);
-        if (e != hipSuccess) rc = fail(MUSE_ERR_HIP, std::string("solver launch: ") + hipGetErrorString(e));
+        if (e == hipErrorNotSupported && shape.jacobi)   // (kernels.hpp, launch_one: nothing was launched)
+            rc = fail(MUSE_ERR_INVALID, "this model's preconditioned implicit-differentiation kernel keeps more than 256 bytes of scratch per "
+                                        "lane (a header too heavy for its registers): MUSE_IMPLICIT_PL_JACOBI is refused for this library "
+                                        "rather than run slower than the loop it replaces -- call without the bit");
+        else if (e != hipSuccess) rc = fail(MUSE_ERR_HIP, std::string("solver launch: ") + hipGetErrorString(e));
     }
     if (rc) return rc;
     if (timed) {
@@ -1581,7 +1587,7 @@ static bool loop_usable(muse_ctx* c, int S, int64_t nlocal, LaunchShape* shape_o
     const int64_t nprob_total = (int64_t)S + 1;
     const int pl = choose_place(c);
     LaunchShape shape;
-    shape.model = c->model; shape.ntheta = nt; shape.place = pl; shape.grid = 0; shape.implicit = false; shape.lds_s = false; shape.taps = false; shape.noise = false;
+    shape.model = c->model; shape.ntheta = nt; shape.place = pl; shape.grid = 0; shape.implicit = false; shape.jacobi = false; shape.lds_s = false; shape.taps = false; shape.noise = false;
     shape.big = false;  // (the loop kernel runs the resident placements)
     shape.done_event = nullptr;
     const bool xg_lds = pl == P_R512x10;
@@ -2122,7 +2128,7 @@ struct CgOptions {   // IterativeSolvers.cg's keywords and get_H!'s implicit_dif
     double reltol, abstol;
     int flags;
 };
-static const double kCgReltolDefault = 1.4901161193847656e-08;   // sqrt(eps): what the kernels of the other models compute themselves
+static const double kCgReltolDefault = 1.4901161193847656e-08;   // sqrt(eps): what the default kernels of the other models compute themselves
 static int implicit_impl(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t e_begin, int64_t e_end, bool per_column,
                          const double* theta0, double atol, const CgOptions& cg, double* cols_out, int32_t* cg_iters_out) {
     const int nt = c->ntheta;
@@ -2132,14 +2138,34 @@ static int implicit_impl(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t 
                                       "supply (MUSE_MODEL_SECOND or MUSE_MODEL_PAIR_SECOND, include/muse_model.h): use the finite-difference entries");
     if (!(cg.reltol >= 0.0) || !(cg.abstol >= 0.0) || !isfinite(cg.reltol) || !isfinite(cg.abstol))
         return fail(MUSE_ERR_INVALID, "cg_reltol and cg_abstol must be finite and >= 0");
-    if (cg.flags & ~MUSE_IMPLICIT_H1_IS_ZERO) return fail(MUSE_ERR_INVALID, "unknown bits in flags");
-#if !(defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_PAIR_SECOND))
-    // The implicit kernels of the built-in models and of the one-parameter family run IterativeSolvers.cg's defaults and always form
-    // H1: anything else is refused, never ignored.
-    if (cg.maxiter < 1 || cg.reltol != kCgReltolDefault || cg.abstol != 0.0 || cg.flags != 0)
+    if (cg.flags & ~(MUSE_IMPLICIT_H1_IS_ZERO | MUSE_IMPLICIT_PL_JACOBI)) return fail(MUSE_ERR_INVALID, "unknown bits in flags");
+    // Which kernels run.  The defaults (and no Jacobi bit) launch the kernels they always launched, which compute sqrt(eps) themselves
+    // and always form H1.  The Jacobi bit launches, for the elementwise models, the instantiations that hold the preconditioned loop and
+    // read every keyword at run time (solver.hpp, run_implicit<true>); a header of the one-parameter family reaches them with any other
+    // keyword too (Pl off: plain CG).  The built-in library without the bit keeps its refusal of those keywords as it always stated it,
+    // and the stencil model has no such kernels: refused, never ignored.
+    const bool pl_jacobi = (cg.flags & MUSE_IMPLICIT_PL_JACOBI) != 0;
+#if defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_PAIR_SECOND)
+    const bool jacobi_kernels = pl_jacobi;   // (the two-parameter family's kernels honour the other keywords already)
+#else
+    const bool defaults = cg.maxiter >= 1 && cg.reltol == kCgReltolDefault && cg.abstol == 0.0 && cg.flags == 0;
+    if (c->model == MUSE_MODEL_SMOOTH && pl_jacobi)
+        return fail(MUSE_ERR_INVALID, "MUSE_IMPLICIT_PL_JACOBI is for the elementwise models, whose Hessian in z is its own diagonal.  The stencil "
+                                      "model's is A' Omega A + diag(e^-theta): its conditioning is the operator's (the near-null space of A times "
+                                      "a large Omega), which no diagonal touches -- Jacobi-preconditioned CG takes as many iterations there as "
+                                      "plain CG, so the bit is refused");
+#if defined(MUSE_USER_MODEL_HEADER)
+    const bool refuses = false;
+#else
+    const bool refuses = !defaults && !pl_jacobi;
+#endif
+    if (refuses)
         return fail(MUSE_ERR_INVALID, "this model's implicit-differentiation kernels run conjugate gradients with cg_reltol = sqrt(eps), "
-                                      "cg_abstol = 0, cg_maxiter >= 1 and form H1: other values are honoured for headers of the "
-                                      "two-parameter family only (MUSE_MODEL_PAIR_SECOND, include/muse_model.h)");
+                                      "cg_abstol = 0, cg_maxiter >= 1 and form H1: other values are honoured together with "
+                                      "MUSE_IMPLICIT_PL_JACOBI (the elementwise built-in models), for headers of the one-parameter family "
+                                      "with second derivatives and for headers of the two-parameter family (MUSE_MODEL_SECOND, "
+                                      "MUSE_MODEL_PAIR_SECOND, include/muse_model.h)");
+    const bool jacobi_kernels = !defaults;
 #endif
     if (ne == 0) return MUSE_OK;
     if (ne > 0x7fffffff) return fail(MUSE_ERR_INVALID, "batch too large");
@@ -2167,7 +2193,7 @@ static int implicit_impl(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t 
     a.slot0 = 0;
     a.scores = c->scores_dev[2];  // [nsims][ntheta][ntheta], H[s][i][j]: only the requested columns are written
     a.info = c->info_dev[2];
-    rc = launch_batch(c, a);
+    rc = launch_batch(c, a, nullptr, jacobi_kernels);
     if (rc) return rc;
     rc = enqueue_results_copy(c, 2, nsims * nt);
     if (rc) return rc;

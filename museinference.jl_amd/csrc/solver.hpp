@@ -2207,6 +2207,60 @@ struct Solver : PairState<Model::kPair> {
     }
 
     // ------------------------------------------------------------------------------------------
+    // The preconditioned CG loop of the JACOBI instantiations (run_implicit<true>, run_implicit_pair<true>), in the order of
+    // IterativeSolvers' preconditioned iterable (cg with the keyword Pl), restated from its published algorithm.  From x = 0, r = b,
+    // u = 0, rho = 1, an iteration is
+    //   c = Pl \ r;  rho' = rho, rho = c.r, beta = rho / rho';  u = c + beta u;  c = A u;  alpha = rho / (u.c);  x += alpha u;  r -= alpha c
+    // and it stops at |r|_2 <= max(cg_reltol |b|_2, cg_abstol) -- the true residual -- or after cg_maxiter iterations.
+    // Two passes and two reductions per iteration: the pass that updates r also forms the NEXT iteration's c.r beside r.r (one
+    // reduce<2, 0>, as everywhere in this solver: one reduction, one barrier), so the caller's right-hand-side pass supplies the first
+    // pair (rr = |b|^2, rho_next = (Pl \ b).b).  Pl = Diagonal(diag(A)) when pl_on (MUSE_IMPLICIT_PL_JACOBI), else the identity:
+    // c_i = r_i / d_i is a division, formed where it is used (in both passes, from the same r and d: the same bits) rather than kept
+    // in a vector -- the passes are bound by their loads and stores, and a stored c or 1/d is one more of each per iteration.
+    // hess_at(jj, i) = h_i = -d_i, hess_times(jj, i, w_i, h_i) = (A w)_i: the caller's operands of its A p product.
+    // Phantom slots and the pad element have r = 0 and possibly h = 0: the select keeps 0/0 out of the sums; a REAL element whose header
+    // says ozz = 0 gets c = 0 instead of inf (include/muse_model.h: Jacobi needs ozz of one sign, A negative definite).
+    static __device__ __forceinline__ double jacobi_solve(double ri, double hi) { return hi != 0.0 ? ri / -hi : 0.0; }
+    template <class HA, class HT>
+    __device__ __forceinline__ int jacobi_cg(double rr, double rho_next, bool pl_on, VH& v, VH& r, VH& u, VH& c, HA&& hess_at, HT&& hess_times) {
+        const int64_t ld = a.ld;
+        const double tol_rel = a.cg_reltol * __builtin_sqrt(rr);
+        const double tol = tol_rel > a.cg_abstol ? tol_rel : a.cg_abstol;
+        double rho = 1.0, mx[1] = {0.0};
+        int it = 0;
+        while (it < a.cg_maxiter && !(__builtin_sqrt(rr) <= tol)) {
+            const double beta = rho_next / rho;
+            rho = rho_next;
+            // ---- u = (Pl \ r) + beta u ; c = A u ; u.c -----------------------------------------------
+            double s1[1] = {0.0};
+            for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
+                const double hi = hess_at(jj, i), ri = r.get(jj, i);
+                const double ui = fma(beta, u.get(jj, i), pl_on ? jacobi_solve(ri, hi) : ri);
+                u.set(jj, i, ui);
+                const double aui = hess_times(jj, i, ui, hi);
+                c.set(jj, i, aui);
+                s1[0] = fma(ui, aui, s1[0]);
+            }, u, c);
+            reduce<1, 0>(s1, mx);
+            const double alpha = rho / s1[0];
+            // ---- x += alpha u ; r -= alpha c ; r.r and the next (Pl \ r).r ---------------------------
+            double s2[2] = {0.0, 0.0};
+            for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
+                v.set(jj, i, fma(alpha, u.get(jj, i), v.get(jj, i)));
+                const double ri = fma(-alpha, c.get(jj, i), r.get(jj, i));
+                r.set(jj, i, ri);
+                s2[0] = fma(ri, ri, s2[0]);
+                s2[1] = fma(pl_on ? jacobi_solve(ri, hess_at(jj, i)) : ri, ri, s2[1]);
+            }, v, r);
+            reduce<2, 0>(s2, mx);
+            rr = s2[0];
+            rho_next = s2[1];
+            it += 1;
+        }
+        return it;
+    }
+
+    // ------------------------------------------------------------------------------------------
     // get_H! implicit-differentiation branch for one simulation (src/muse.jl:335-405):
     //   H = H1 - dFdtheta^T A^{-1} dFdtheta1,  A = Hessian_z logLike at (x, zhat, theta0),
     // A^{-1} by conjugate gradients (IterativeSolvers.cg: x0 = 0, reltol sqrt(eps), abstol 0, maxiter).
@@ -2215,7 +2269,12 @@ struct Solver : PairState<Model::kPair> {
     // the CG vectors reuse the solver's g, s and history buffers; z_true sits in the extra vector.
     // Writes H[p] (row-major ntheta x ntheta) and the CG iteration count of column j to info[p*ntheta+j].
     // (The two-parameter family has a branch of its own, run_implicit_pair below: the kernel picks it, kernels.hpp.)
+    // JACOBI (elementwise models; kernels of their own, kernels.hpp): every keyword of IterativeSolvers.cg at run time -- cg_reltol,
+    // cg_abstol, cg_maxiter = 0, H1-is-zero -- and the loop of its preconditioned iterable, whose Pl is the identity unless
+    // MUSE_IMPLICIT_PL_JACOBI says Diagonal(diag(A)) (jacobi_cg below).
+    template <bool JACOBI = false>
     __device__ __forceinline__ void run_implicit(int p, double* wg_scratch, double* lds_x, double* lds_g) {
+        static_assert(!JACOBI || !Model::kStencil, "the preconditioned loop is the elementwise models'");
         begin<true>(p, wg_scratch, lds_x, lds_g);
         solve(p);
         const int64_t ld = a.ld;
@@ -2243,9 +2302,24 @@ struct Solver : PairState<Model::kPair> {
         const int plist = p + a.p0;  // position in the list that starts at sim_begin's first column
         const int64_t psim = plist / split;
         const int j_lo = split > 1 ? plist % split : 0, j_hi = split > 1 ? j_lo + 1 : nth;
+        const bool h1_zero = JACOBI && (a.imp_flags & MUSE_IMPLICIT_H1_IS_ZERO) != 0;
+        const bool pl_on = JACOBI && (a.imp_flags & MUSE_IMPLICIT_PL_JACOBI) != 0;
+        // JACOBI: h_i = -diag(A)_i and (A w)_i, in the operands and the expressions of the A p product of the loop below.  Noise and the
+        // user model: A w IS -(h w), the same rounded h.  Funnel: the loop's product is -(w + iv w), kept as it is, while h = 1 + iv is
+        // rounded once -- the two differ by a rounding, which leaves the first residual at a few ulp of |b| (tolerance: sqrt(eps) |b|).
+        auto hess_at = [&](int jj, int i) {
+            if constexpr (Model::kId == MUSE_MODEL_NOISE) return iv0 + 1.0;
+            else if constexpr (Model::kId == MUSE_MODEL_USER) return t1.get(jj, i);
+            else return 1.0 + ivk(jj, i);
+        };
+        auto hess_times = [&](int jj, int i, double wi, double hi) {
+            if constexpr (Model::kId == MUSE_MODEL_NOISE || Model::kId == MUSE_MODEL_USER) return -(hi * wi);
+            else return -(wi + ivk(jj, i) * wi);
+        };
         for (int j = j_lo; j < j_hi; ++j) {
             // ---- right-hand side b = dFdtheta1[:, j]; v = 0, r = p = b --------------------------------
             double sum[1] = {0.0}, mx[1] = {0.0};
+            double sum2[2] = {0.0, 0.0};   // JACOBI: r.r and c.r, c = Pl \ r
             if constexpr (Model::kStencil) {
                 for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
                     const double zt = ztrue.get(jj, i);  // unconditional: the pair load is issued at the even element
@@ -2265,26 +2339,39 @@ struct Solver : PairState<Model::kPair> {
                 for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
                     const double zt = ztrue.get(jj, i);  // unconditional: the pair load is issued at the even element
                     double bi;
+                    [[maybe_unused]] double hi = 0.0;   // JACOBI: -diag(A)_i (hess_at; the user model's is on its way to t1)
+                    if constexpr (JACOBI && Model::kId != MUSE_MODEL_USER) hi = hess_at(jj, i);
                     if constexpr (Model::kId == MUSE_MODEL_NOISE) bi = iv0 * (0.5 * (x.get(jj, i) - zt));
                     else if constexpr (Model::kId == MUSE_MODEL_USER) {
                         // zt is dx_i / dtheta_k here (keep_value); the element's d2 o / dz2 goes to t1 for the CG passes
                         double ozz, ozx, bz, bx;
                         Model::second(ivk(jj, i), x.get(jj, i), z.get(jj, i), ozz, ozx, bz, bx, i);
                         t1.set(jj, i, ozz);
+                        hi = ozz;
                         const double bb = -(ozx * zt);
                         bi = blk(jj, i) == j ? bb : 0.0;
                     }
                     else bi = blk(jj, i) == j ? 0.5 * zt : 0.0;
                     v.set(jj, i, 0.0);
                     r.set(jj, i, bi);
+                    if constexpr (JACOBI) {   // u = 0; the first c.r beside |b|^2 (jacobi_cg)
+                        pp.set(jj, i, 0.0);
+                        sum2[0] = fma(bi, bi, sum2[0]);
+                        sum2[1] = fma(pl_on ? jacobi_solve(bi, hi) : bi, bi, sum2[1]);
+                    } else {
                     pp.set(jj, i, bi);
                     sum[0] = fma(bi, bi, sum[0]);
+                    }
                 }, v, r, pp, when(Model::kId == MUSE_MODEL_USER, t1));
             }
+            int it = 0;
+            if constexpr (JACOBI) {
+                reduce<2, 0>(sum2, mx);
+                it = jacobi_cg(sum2[0], sum2[1], pl_on, v, r, pp, Ap, hess_at, hess_times);
+            } else {
             reduce<1, 0>(sum, mx);
             double rr = sum[0];
             const double tol = __builtin_sqrt(kEps) * __builtin_sqrt(rr);
-            int it = 0;
             while (it < a.cg_maxiter && !(__builtin_sqrt(rr) <= tol)) {
                 // ---- Ap = A_hess p, p.Ap -----------------------------------------------------------
                 double s1[1] = {0.0};
@@ -2327,6 +2414,7 @@ struct Solver : PairState<Model::kPair> {
                 }, pp);
                 if constexpr (Model::kStencil) pass_barrier();
                 it += 1;
+            }
             }
             // ---- H[:, j] = H1[:, j] - dFdtheta^T v ----------------------------------------------------
             // (big tier: eight rows of the column per pass, as finish() forms its block sums)
@@ -2379,6 +2467,7 @@ struct Solver : PairState<Model::kPair> {
                                 const double ivj = kBig ? big_iv[j] : a.cur.t.iv[j];
                                 h1 = c + b == j ? 0.5 * (ivj * h1u[0]) : 0.0;
                             }
+                            if constexpr (JACOBI) h1 = h1_zero ? 0.0 : h1;   // (src/muse.jl:353; the sums are cheap beside the pass and stay)
                             a.scores[(psim * nth + c + b) * nth + j] = h1 - acc[b];
                         }
                     }
@@ -2407,6 +2496,9 @@ struct Solver : PairState<Model::kPair> {
     // (the same generator sequence, so the same bits) and stores xa in the extra vector and xb in the fourth history vector, which
     // the elementwise CG does not use -- the L-BFGS history is dead once the solve has ended -- together with ozz for the CG passes.
     // CG stops at |r| <= max(cg_reltol |b|, cg_abstol) or after cg_maxiter iterations (0: H = H1).
+    // JACOBI (kernels of their own, kernels.hpp): the preconditioned loop, Pl = Diagonal(-ozz) (jacobi_cg above).  Every history
+    // vector is taken (p / u, A p, ozz, xb), so c = r / d is formed where it is used; the diagonal is t1, which the loop reads anyway.
+    template <bool JACOBI = false>
     __device__ __forceinline__ void run_implicit_pair(int p, double* wg_scratch, double* lds_x, double* lds_g) {
         begin<true>(p, wg_scratch, lds_x, lds_g);
         solve(p);
@@ -2438,11 +2530,13 @@ struct Solver : PairState<Model::kPair> {
         const int64_t psim = plist / split;
         const int j_lo = split > 1 ? plist % split : 0, j_hi = split > 1 ? j_lo + 1 : nth;
         const bool h1_zero = (a.imp_flags & 1) != 0;
+        const bool pl_on = JACOBI && (a.imp_flags & MUSE_IMPLICIT_PL_JACOBI) != 0;
         for (int j = j_lo; j < j_hi; ++j) {
             const int kb = j < K ? j : j - K;   // the column's block; its parameter kind selects the draw's derivative
             xq.bind(j < K ? extra : hist + 3 * ld, ld);
             // ---- right-hand side b = dFdtheta1[:, j]; v = 0, r = p = b --------------------------------
             double sum[1] = {0.0}, mx[1] = {0.0};
+            double sum2[2] = {0.0, 0.0};   // JACOBI: r.r and c.r, c = Pl \ r
             for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
                 const double dxi = xq.get(jj, i);  // unconditional: the pair load is issued at the even element
                 double q[6];
@@ -2451,14 +2545,25 @@ struct Solver : PairState<Model::kPair> {
                 const double bi = blk(jj, i) == kb ? bb : 0.0;
                 v.set(jj, i, 0.0);
                 r.set(jj, i, bi);
+                if constexpr (JACOBI) {   // u = 0; the first c.r beside |b|^2 (q[0] is what t1 holds: the same call, the same bits)
+                    pp.set(jj, i, 0.0);
+                    sum2[0] = fma(bi, bi, sum2[0]);
+                    sum2[1] = fma(pl_on ? jacobi_solve(bi, q[0]) : bi, bi, sum2[1]);
+                } else {
                 pp.set(jj, i, bi);
                 sum[0] = fma(bi, bi, sum[0]);
+                }
             }, v, r, pp);
+            int it = 0;
+            if constexpr (JACOBI) {
+                reduce<2, 0>(sum2, mx);
+                it = jacobi_cg(sum2[0], sum2[1], pl_on, v, r, pp, Ap, [&](int jj, int i) { return t1.get(jj, i); },
+                               [&](int, int, double wi, double hi) { return -(hi * wi); });
+            } else {
             reduce<1, 0>(sum, mx);
             double rr = sum[0];
             const double tol_rel = a.cg_reltol * __builtin_sqrt(rr);
             const double tol = tol_rel > a.cg_abstol ? tol_rel : a.cg_abstol;
-            int it = 0;
             while (it < a.cg_maxiter && !(__builtin_sqrt(rr) <= tol)) {
                 // ---- Ap = A_hess p, p.Ap -----------------------------------------------------------
                 double s1[1] = {0.0};
@@ -2486,6 +2591,7 @@ struct Solver : PairState<Model::kPair> {
                     pp.set(jj, i, fma(beta, pp.get(jj, i), r.get(jj, i)));
                 }, pp);
                 it += 1;
+            }
             }
             // ---- H[:, j] = H1[:, j] - dFdtheta^T v: rows k and K + k of every block, the two H1 sums of the column's block ----
             double acc[MAXB], h1s[2] = {0.0, 0.0};

@@ -301,7 +301,7 @@ class ShardedMuseProblem:
 
     def implicit_H_batch(self, rng, sim_begin, sim_end, theta0, *, atol=1e-1, cg_maxiter=100, **cg):
         """get_H! implicit-differentiation branch (src/muse.jl:335-405), the (sim, column) units shared like the
-        finite-difference ones.  cg: cg_reltol, cg_abstol, H1_is_zero, passed on to the local problem."""
+        finite-difference ones.  cg: cg_reltol, cg_abstol, H1_is_zero, cg_Pl, passed on to the local problem."""
         nth = np.atleast_1d(theta0).size
         if hasattr(self.local, "implicit_H_columns"):
             ncol = (sim_end - sim_begin) * nth

@@ -156,7 +156,10 @@ def check_model_consistency(prob, theta, rng=0, n_probe=6, step=1e-5, rtol=2e-5)
 
         the second derivatives of a header with MUSE_MODEL_SECOND or MUSE_MODEL_PAIR_SECOND (what the implicit-differentiation
                                  get_H! builds on) against central differences of the header's own first-order functions
-                                 (_check_second, _check_pair_second: "second"),
+                                 (_check_second, _check_pair_second: "second").  CG preconditioned by the Hessian's diagonal
+                                 (implicit_diff_cg_kwargs={"Pl": "jacobi"}) relies on more than their correctness: d2 o / dz2 must
+                                 have ONE sign over the run (a negative-definite Hessian of logLike), and a header that says 0 on a
+                                 real element gets c_i = 0 there from the kernel's select, not inf (include/muse_model.h),
 
     and returns {"grad_z": worst residual, "grad_theta": worst residual, "noise_floor": ...} -- residuals relative to the larger
     of the gradient's size and 1; noise_floor: what the rounding of logLike (a sum of N terms) alone puts into such a

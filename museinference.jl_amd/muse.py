@@ -9,6 +9,7 @@ A problem that does not provide the batched seams (any other AbstractMuseProblem
 element by element through sample_x_z / zhat_at_theta / grad_theta_logLike, i.e. the reference's
 LocalWorkerPool path (src/util.jl:74-76).
 """
+import inspect
 import math
 import pickle
 import time
@@ -433,8 +434,10 @@ def _fd_batched(prob, rng, nsims, theta0, m, step, atol, fid_mode):
 
 def _cg_keywords(cg_kwargs):
     """implicit_diff_cg_kwargs (splatted into IterativeSolvers.cg by the reference, src/muse.jl:381) as the keywords of the
-    implicit_H_batch seam: maxiter, reltol, abstol; Pl only as the identity (None or an identity matrix: no preconditioners here).
-    Any other key is an error, never ignored."""
+    implicit_H_batch seam: maxiter, reltol, abstol; Pl as the identity (None or an identity matrix) or the string "jacobi" -- the
+    diagonal of the Hessian the branch applies, formed by the kernel itself (the reference's users pass Diagonal(...) of it, which a
+    closure cannot carry across the C ABI): cg_Pl="jacobi" at the seam, only when given.  Any other key or Pl is an error, never
+    ignored."""
     kw = dict(cg_kwargs or {})
     out = {"cg_maxiter": int(kw.pop("maxiter", 100))}
     if "reltol" in kw:
@@ -443,26 +446,46 @@ def _cg_keywords(cg_kwargs):
         out["cg_abstol"] = float(kw.pop("abstol"))
     if "Pl" in kw:
         Pl = kw.pop("Pl")
-        if Pl is not None:
+        if isinstance(Pl, str):
+            if Pl != "jacobi":
+                raise ValueError(f'implicit_diff_cg_kwargs: Pl must be the identity (None or an identity matrix) or "jacobi" (the '
+                                 f"Hessian's diagonal, formed in the kernel); got {Pl!r}")
+            out["cg_Pl"] = "jacobi"
+        elif Pl is not None:
             try:
                 P = np.asarray(Pl, dtype=np.float64)
             except (TypeError, ValueError):
                 P = None
             if P is None or P.ndim != 2 or P.shape[0] != P.shape[1] or not np.array_equal(P, np.eye(P.shape[0])):
-                raise ValueError("implicit_diff_cg_kwargs: Pl must be the identity (None or an identity matrix): preconditioners are "
-                                 "not supported")
+                raise ValueError('implicit_diff_cg_kwargs: Pl must be the identity (None or an identity matrix) or "jacobi" (the '
+                                 "Hessian's diagonal, formed in the kernel): a matrix or a closure of the caller's does not cross the "
+                                 "C ABI")
     if kw:
-        raise ValueError(f"implicit_diff_cg_kwargs: unsupported key(s) {sorted(kw)} (supported: maxiter, reltol, abstol, Pl = identity)")
+        raise ValueError(f"implicit_diff_cg_kwargs: unsupported key(s) {sorted(kw)} (supported: maxiter, reltol, abstol, "
+                         f'Pl = identity or "jacobi")')
     return out
+
+
+def _seam_takes(prob, keyword):
+    """Whether prob.implicit_H_batch exists and accepts `keyword` (by name or through **keywords) -- asked before the problem is touched."""
+    seam = getattr(prob, "implicit_H_batch", None)
+    try:
+        params = inspect.signature(seam).parameters
+    except (TypeError, ValueError):
+        return False
+    return keyword in params or any(p.kind is p.VAR_KEYWORD for p in params.values())
 
 
 def _get_H_implicit(result, prob, theta0, rng, nsims, cg_kwargs, skip_errors, H1_is_zero=False):
     """get_H! with implicit_diff=true (src/muse.jl:335-405): H = H1 - dFdθᵀ A⁻¹ dFdθ1 per sim, A⁻¹ by CG
-    (implicit_diff_cg_kwargs default (maxiter=100, Pl=I); reltol and abstol are passed on); implicit_diff_H1_is_zero skips H1
+    (implicit_diff_cg_kwargs default (maxiter=100, Pl=I); reltol, abstol and Pl="jacobi" are passed on); implicit_diff_H1_is_zero skips H1
     (src/muse.jl:353); the fiducial MAP is solved to 1e-1 as the reference hard-codes (src/muse.jl:344).  CG iteration counts go to
     metadata["implicit_diff_cg_hists"].  A keyword beyond atol and cg_maxiter reaches the problem only when it is given, so that a
     problem whose seam does not know it says so instead of ignoring it."""
     cg = _cg_keywords(cg_kwargs)
+    if "cg_Pl" in cg and not _seam_takes(prob, "cg_Pl"):
+        raise ValueError('implicit_diff_cg_kwargs: Pl must be the identity (None or an identity matrix) for this problem: "jacobi" needs '
+                         "an implicit_H_batch seam that takes cg_Pl")
     if H1_is_zero:
         cg["H1_is_zero"] = True
     rng = int(_something(rng, result.rng, _default_rng()))

@@ -593,21 +593,26 @@ class HipMuseProblem(AbstractMuseProblem):
         return Hs, info
 
     @staticmethod
-    def _cg_options(cg_reltol, cg_abstol, H1_is_zero):
+    def _cg_options(cg_reltol, cg_abstol, H1_is_zero, cg_Pl=None):
+        if cg_Pl is not None and cg_Pl != "jacobi":
+            raise ValueError(f'cg_Pl must be None (the identity) or "jacobi", got {cg_Pl!r}')
         return (float(np.sqrt(np.finfo(np.float64).eps)) if cg_reltol is None else float(cg_reltol), float(cg_abstol),
-                _capi.IMPLICIT_H1_IS_ZERO if H1_is_zero else 0)
+                (_capi.IMPLICIT_H1_IS_ZERO if H1_is_zero else 0) | (_capi.IMPLICIT_PL_JACOBI if cg_Pl == "jacobi" else 0))
 
     def implicit_H_batch(self, rng, sim_begin, sim_end, theta0, *, atol=1e-1, cg_maxiter=100, cg_reltol=None, cg_abstol=0.0,
-                         H1_is_zero=False):
+                         H1_is_zero=False, cg_Pl=None):
         """get_H! implicit-differentiation branch for sims [sim_begin, sim_end): (Hs [nsims, nθ, nθ],
         cg iteration counts [nsims, nθ])   [src/muse.jl:335-405].  Conjugate gradients stop at |r| <= max(cg_reltol |b|, cg_abstol)
-        (default sqrt(eps), 0) or after cg_maxiter iterations; H1_is_zero skips the H1 term (implicit_diff_H1_is_zero).  Values other
-        than the defaults are honoured for models of the two-parameter family and refused for every other model."""
+        (default sqrt(eps), 0) or after cg_maxiter iterations; H1_is_zero skips the H1 term (implicit_diff_H1_is_zero);
+        cg_Pl="jacobi" preconditions CG by the Hessian's diagonal (MUSE_IMPLICIT_PL_JACOBI: one iteration per column for the
+        elementwise models).  Values other than the defaults are honoured for a user's header with second derivatives (either
+        family) and, together with cg_Pl="jacobi", for the built-in funnel and noise models; the built-in models without it, and the
+        stencil model (smooth) always, refuse them."""
         th = self._theta(theta0)
         ns = sim_end - sim_begin
         Hs = np.empty((ns, self.ntheta, self.ntheta))
         its = np.zeros((ns, self.ntheta), dtype=np.int32)
-        reltol, abstol, flags = self._cg_options(cg_reltol, cg_abstol, H1_is_zero)
+        reltol, abstol, flags = self._cg_options(cg_reltol, cg_abstol, H1_is_zero, cg_Pl)
         self._check(self._lib.muse_implicit_H_batch_ex(self._ctx, _seed_of(rng), sim_begin, sim_end, _capi.ptr(th), float(atol),
                                                        int(cg_maxiter), reltol, abstol, flags, _capi.ptr(Hs), _capi.ptr(its)))
         return Hs, its
@@ -649,13 +654,13 @@ class HipMuseProblem(AbstractMuseProblem):
         return F, info
 
     def implicit_H_columns(self, rng, sim_begin, col_begin, col_end, theta0, *, atol=1e-1, cg_maxiter=100, cg_reltol=None,
-                           cg_abstol=0.0, H1_is_zero=False):
+                           cg_abstol=0.0, H1_is_zero=False, cg_Pl=None):
         """The same column range for the implicit-differentiation H: (cols [n, nθ], cg iteration counts [n])."""
         th = self._theta(theta0)
         n = col_end - col_begin
         cols = np.empty((n, self.ntheta))
         its = np.zeros(n, dtype=np.int32)
-        reltol, abstol, flags = self._cg_options(cg_reltol, cg_abstol, H1_is_zero)
+        reltol, abstol, flags = self._cg_options(cg_reltol, cg_abstol, H1_is_zero, cg_Pl)
         self._check(self._lib.muse_implicit_H_columns_ex(self._ctx, _seed_of(rng), sim_begin, col_begin, col_end, _capi.ptr(th),
                                                          float(atol), int(cg_maxiter), reltol, abstol, flags, _capi.ptr(cols),
                                                          _capi.ptr(its)))
