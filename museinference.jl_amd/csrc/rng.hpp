@@ -29,6 +29,30 @@ struct NormalPair {
 // sequence it always was (K = 1 is the scalar definition the oracle restates).
 #define MUSE_K for (int k = 0; k < K; ++k)
 
+// a ^ b ^ c.  gfx950 has a three-input bitwise operation with an 8-bit truth table (v_bitop3_b32; 0x96 is the parity
+// of the three bits) at the cost of one two-input xor (tools/clockprobe.hip, profiles/r07_clockprobe_bitop3.log); the compiler
+// does not form it from two xors on its own.  The truth table is an immediate of the instruction: it stays a literal.
+#if defined(__has_builtin)
+#if __has_builtin(__builtin_amdgcn_bitop3_b32)
+#define MUSE_HAVE_BITOP3 1
+#endif
+#endif
+__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
+#ifdef MUSE_HAVE_BITOP3
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+#else
+    return a ^ b ^ c;
+#endif
+}
+// a ^ (b & ~c), the same instruction with the truth table 0xb4.
+__device__ __forceinline__ uint32_t xor_andn(uint32_t a, uint32_t b, uint32_t c) {
+#ifdef MUSE_HAVE_BITOP3
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0xb4);
+#else
+    return a ^ (b & ~c);
+#endif
+}
+
 // IEEE division a / b for operands in the normal range with a normal quotient (here b in [1.29, 2.42], |a| < 0.42):
 // v_rcp_f64 + two Newton-Raphson steps + one correction, i.e. the sequence the compiler emits for `/` without the
 // operand rescaling (v_div_scale), the scaled fma (v_div_fmas, which goes through VCC and so cannot interleave with
@@ -156,8 +180,13 @@ __device__ __forceinline__ void sincospi_02(const double (&t)[K], double (&sn)[K
         const bool swap = (n[k] & 1) != 0;
         const double a = swap ? kc[k] : ks[k];  // |sin|
         const double b = swap ? ks[k] : kc[k];  // |cos|
-        sn[k] = (n[k] & 2) ? -a : a;
-        cs[k] = ((n[k] + 1) & 2) ? -b : b;
+        // sn = (n & 2) ? -a : a, cs = ((n + 1) & 2) ? -b : b as an xor into the sign bit (the same bits: a negation is that
+        // xor): bit 1 of n, and of n + 1, moved to bit 31 -- two instructions per value where the compare, the negation
+        // and the select were four, and no VCC between neighbouring chains.  (n <= 4: the shift leaves bits 31 and 30; bit 30 is
+        // masked by 0x40000000, which is an inline constant -- the pattern of 2.0f -- where 0x80000000 would take a register.)
+        const uint32_t qs = (uint32_t)n[k] << 30, qc = ((uint32_t)n[k] << 30) + 0x40000000u;
+        sn[k] = __hiloint2double((int)xor_andn((uint32_t)__double2hiint(a), qs, 0x40000000u), __double2loint(a));
+        cs[k] = __hiloint2double((int)xor_andn((uint32_t)__double2hiint(b), qc, 0x40000000u), __double2loint(b));
     }
 }
 
@@ -210,7 +239,7 @@ __device__ __forceinline__ void philox4x32_10(const uint64_t (&i)[K], uint64_t s
         MUSE_K p1[k] = (uint64_t)0xCD9E8D57u * c2[k];
 #pragma unroll
         MUSE_K {
-            const uint32_t n0 = (uint32_t)(p1[k] >> 32) ^ c1[k] ^ k0, n2 = (uint32_t)(p0[k] >> 32) ^ c3[k] ^ k1;
+            const uint32_t n0 = xor3((uint32_t)(p1[k] >> 32), c1[k], k0), n2 = xor3((uint32_t)(p0[k] >> 32), c3[k], k1);
             c1[k] = (uint32_t)p1[k];
             c3[k] = (uint32_t)p0[k];
             c0[k] = n0;

@@ -1478,6 +1478,10 @@ struct Solver : PairState<Model::kPair> {
                     // block).  At the two waves per SIMD of this placement a wave issues a VALU instruction every ~5.3 cycles
                     // when it has four independent ones to choose from and every ~11 when each depends on the one before
                     // (tools/clockprobe.hip): with one pair per trip the generator ran at ~9.8 cycles per instruction.
+                    // The true z is staged in the g area only for the start that reads it back (Z0_TRUE, below), as in the cached
+                    // branch above.  The gate is workgroup-uniform and sits with the stores behind the trip's arithmetic, which the
+                    // uniform branch around the normals' store already ends: the chains' block is untouched.
+                    const bool stage_ztrue = d.z0_mode == Z0_TRUE;
                     auto draw = [&](auto npairs, int i0, int j) {
                         // both elements of a pair unconditionally; for odd N the last pair's second element is the pad
                         // slot, kept at 0.  All 2 * P generator chains advance side by side (rng.hpp).
@@ -1502,9 +1506,11 @@ struct Solver : PairState<Model::kPair> {
                             Model::sample(sd_of(2 * (j + q) + 1), np[2 * q + 1].n1, np[2 * q + 1].n2, zt1, xt1, j0 + 1);
                             const bool valid1 = j0 + 1 < (int)N;
                             x.p[j0] = xt0;
-                            g.p[j0] = zt0;
                             x.p[j0 + 1] = valid1 ? xt1 : 0.0;
-                            g.p[j0 + 1] = valid1 ? zt1 : 0.0;
+                            if (stage_ztrue) {
+                                g.p[j0] = zt0;
+                                g.p[j0 + 1] = valid1 ? zt1 : 0.0;
+                            }
                         }
                     };
                     int j = 0;  // the pair's slot: pair j of this thread is elements i0, i0 + 1 with i0 = 2 (tid + j T)

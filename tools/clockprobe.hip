@@ -1,6 +1,6 @@
 // VALU issue/latency probe (development aid): every workgroup runs C independent chains of dependent fp64 FMAs (mode 0),
 // 64-bit integer multiply-adds v_mad_u64_u32 (mode 1), fp64 multiplies (mode 2), fp64 adds (mode 3) or 32-bit integer
-// xors (mode 4), and reads s_memtime (shader clocks; s_memrealtime, 100 MHz, gives the clock) around the loop.
+// xors (mode 4) or three-input bitwise ops v_bitop3_b32 with the a ^ b ^ c truth table (mode 5: three vector sources, mode 6: one scalar source), and reads s_memtime (shader clocks; s_memrealtime, 100 MHz, gives the clock) around the loop.
 // Prints shader cycles per instruction per wave at 1 and 2 waves per SIMD.  usage: clockprobe [iters]
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -12,12 +12,14 @@ template <int MODE, int C>
 __global__ void __launch_bounds__(1024) probe(unsigned long long* out, int iters, double seed) {
     double a[C];
     unsigned long long m[C];
-    unsigned x[C];
+    unsigned x[C], y[C];
     for (int c = 0; c < C; ++c) {
         a[c] = seed + threadIdx.x + c;
         m[c] = threadIdx.x + 12345 + c;
         x[c] = threadIdx.x * 7 + c;
+        y[c] = threadIdx.x * 13 + c;
     }
+    const unsigned sk = (unsigned)iters * 0x9E3779B9u;
     const double b = 1.0000001, k = 0.5;
     unsigned long long t0, r0, t1, r1;
     asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0), "=s"(r0)::"memory");
@@ -31,6 +33,8 @@ __global__ void __launch_bounds__(1024) probe(unsigned long long* out, int iters
                 if (MODE == 2) asm volatile("v_mul_f64 %0, %0, %1" : "+v"(a[c]) : "v"(b));
                 if (MODE == 3) asm volatile("v_add_f64 %0, %0, %1" : "+v"(a[c]) : "v"(k));
                 if (MODE == 4) asm volatile("v_xor_b32 %0, %0, %1" : "+v"(x[c]) : "v"(0x9E3779B9u));
+                if (MODE == 5) asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:0x96" : "+v"(x[c]) : "v"(0x9E3779B9u), "v"(y[c]));
+                if (MODE == 6) asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:0x96" : "+v"(x[c]) : "v"(y[c]), "s"(sk));   // one scalar source, as the round's key word
             }
         }
     }
@@ -85,5 +89,7 @@ int main(int argc, char** argv) {
     run<0, 1>(d, iters, "v_fma_f64"); run<0, 4>(d, iters, "v_fma_f64"); run<0, 8>(d, iters, "v_fma_f64");
     run<1, 1>(d, iters, "v_mad_u64_u32"); run<1, 4>(d, iters, "v_mad_u64_u32");
     run<4, 1>(d, iters, "v_xor_b32"); run<4, 4>(d, iters, "v_xor_b32");
+    run<5, 1>(d, iters, "v_bitop3_b32"); run<5, 4>(d, iters, "v_bitop3_b32");
+    run<6, 1>(d, iters, "v_bitop3_b32 vvs"); run<6, 4>(d, iters, "v_bitop3_b32 vvs");
     return 0;
 }
