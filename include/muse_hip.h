@@ -167,6 +167,26 @@ int muse_set_noise(muse_ctx* ctx, const double* sd /* N, finite, > 0 */, const d
 /* The noise in use: sd_out[N] and mask_out[N] as they were set (all 1 without), *runtime_out = 1 when the launches read noise vectors
  * and 0 for the kernels without; any pointer may be NULL.  MUSE_ERR_INVALID for another model. */
 int muse_get_noise(muse_ctx* ctx, double* sd_out, double* mask_out, int* runtime_out);
+/* A pointwise response behind the operator of MUSE_MODEL_SMOOTH as context state -- a blurred field seen through a detector with gain
+ * compression or a quadratic / cubic non-linearity, with everything the model has otherwise (stencil, noise map, mask):
+ *     u = A z,   x_i = phi(u_i) + s_i n2_i,   phi(u) = u + a2 u^2 + a3 u^3,   phi'(u) = 1 + 2 a2 u + 3 a3 u^2,
+ *     -logLike = 1/2 sum_i omega_i r_i^2 + 1/2 sum_i e^{-theta_k} z_i^2 + 1/2 sum_k n_k theta_k,   r = x - phi(A z),
+ *     grad_z (-logLike) = e^{-theta} z - A' (omega phi'(u) r);   the score is unchanged (phi does not depend on theta).
+ * a = {a2, a3}; any finite pair is accepted.  For a2^2 < 3 a3 phi is strictly increasing; a response that is not monotone makes the
+ * posterior in z multi-modal -- the MAP found then depends on the start, which is the caller's business.  Once set, EVERY entry point
+ * that takes the context uses the link (per-simulation operators, batched / multi / gathered maps, the finite-difference get_H!
+ * entries, muse_run*): the coefficients travel in each launch's own argument block, so the call waits for nothing and contexts with
+ * different links may have launches in flight together.  With a = {0, 0} the results are those of the context without a link, bit
+ * for bit (from the kernels with a link: muse_get_link reports runtime 1).
+ * a == NULL: no link, AND the kernels the context launched before.
+ * The implicit-differentiation get_H! (muse_implicit_H_*) of a context with a link is refused with MUSE_ERR_INVALID: the Hessian is
+ * A' diag(omega (phi'^2 - r phi'')) A + diag(e^-theta), which the r phi'' term can make indefinite away from the MAP.
+ * MUSE_ERR_INVALID: another model, a library built from a user's model header, a coefficient that is not finite -- the context keeps
+ * the link it had. */
+int muse_set_link(muse_ctx* ctx, const double* a /* {a2, a3}, or NULL: no link and the kernels without */);
+/* The link in use: a_out[2] = {a2, a3} ({0, 0} without), *runtime_out = 1 when the launches apply a link and 0 for the kernels
+ * without; either pointer may be NULL.  MUSE_ERR_INVALID for another model. */
+int muse_get_link(muse_ctx* ctx, double* a_out, int* runtime_out);
 /* The functions of a user-supplied model's header evaluated on the HOST for one element (include/muse_model.h) -- what the
  * reference gets from AD for free has to be checkable for hand-written derivatives (src/simple.jl:84-85): Python's
  * check_model_consistency differentiates these values numerically.  out[10] = { muse_model_grad's return value, the objective

@@ -269,6 +269,18 @@ function get_noise(prob::HipMuseProblem)
     check(ccall((:muse_get_noise, libmuse_hip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}), prob.ctx, sd, mask, rt))
     (; sd=sd, mask=mask .!= 0, runtime=rt[] != 0)
 end
+# A pointwise response behind the operator of the "smooth" model as state of the problem (include/muse_hip.h: muse_set_link):
+# x_i = phi((A z)_i) + sd_i n_i, phi(u) = u + a2 u^2 + a3 u^3, any finite pair -- used by every operator, map and finite-difference
+# get_H! from the next call on (the implicit-differentiation branch is refused while a link is set); `nothing`: no link and the
+# kernels that ran before.
+set_link(prob::HipMuseProblem, a::Union{Nothing,NTuple{2,Real}}) =
+    check(ccall((:muse_set_link, libmuse_hip), Cint, (Ptr{Cvoid}, Ptr{Float64}), prob.ctx,
+                a === nothing ? C_NULL : Float64[a[1], a[2]]))
+function get_link(prob::HipMuseProblem)
+    a = Vector{Float64}(undef, 2); rt = Ref{Cint}(0)
+    check(ccall((:muse_get_link, libmuse_hip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cint}), prob.ctx, a, rt))
+    (; link=(a[1], a[2]), runtime=rt[] != 0)
+end
 # plain maps over simulations the context has drawn before load their standard normals instead of generating them: off / on
 set_normals_cache(prob::HipMuseProblem, enabled::Bool) =
     check(ccall((:muse_set_normals_cache, libmuse_hip), Cint, (Ptr{Cvoid}, Cint), prob.ctx, enabled))

@@ -84,6 +84,8 @@ SIGNATURES = {
     "muse_get_stencil": (_i, [_vp, _vp, C.POINTER(_i)]),
     "muse_set_noise": (_i, [_vp, _vp, _vp, _i]),
     "muse_get_noise": (_i, [_vp, _vp, _vp, C.POINTER(_i)]),
+    "muse_set_link": (_i, [_vp, _vp]),
+    "muse_get_link": (_i, [_vp, _vp, C.POINTER(_i)]),
     "muse_model_eval": (_i, [_vp, _d, _d, _d, _d, _d, _d, _i64, _vp]),
     "muse_model_eval_pair_second": (_i, [_vp, _d, _d, _d, _d, _d, _d, _i64, _vp]),
     "muse_model_has_second": (_i, []),

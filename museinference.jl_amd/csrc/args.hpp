@@ -175,6 +175,12 @@ struct BatchArgs {
         // (muse_set_stencil; models.hpp, SmoothTapsModel): per LAUNCH like the constants, and in the place of their lengths -- a
         // library holds either the built-in models or a user's, and sizeof(BatchArgs) is where the loop kernels find LoopArgs
         double taps[kStencilWeights];
+        // ... and behind them, kernarg segment only, the coefficients {a2, a3} of the stencil model's response phi(u) = u + a2 u^2 + a3 u^3
+        // when the context has one (muse_set_link; models.hpp, SmoothLinkModel): the other 16 bytes of the lengths' place
+        struct {
+            double taps_[kStencilWeights];
+            double link[2];
+        };
     };
     // kernarg segment only: gran_sys == 2 -- the sharded loop with a board per GPU in DEVICE memory (muse_comm.cpp: every rank's board
     // is mapped into every rank by hipIpc): an element's score granules are stored into EVERY rank's board (posted writes over xGMI),
@@ -185,6 +191,9 @@ struct BatchArgs {
 constexpr size_t kArgsConstsOffset = offsetof(BatchArgs, consts);
 static_assert(offsetof(BatchArgs, const_len) == kArgsConstsOffset + 4 * sizeof(const double*), "muse_const reads {pointers[4], lengths[4]}");
 static_assert(sizeof(double) * kStencilWeights <= sizeof(long) * 4 && offsetof(BatchArgs, taps) % 16 == 0, "the weights take the place of const_len: one aligned scalar load");
+static_assert(offsetof(BatchArgs, link) == offsetof(BatchArgs, taps) + sizeof(double) * kStencilWeights && offsetof(BatchArgs, link) % 16 == 0 &&
+              offsetof(BatchArgs, link) + 2 * sizeof(double) == offsetof(BatchArgs, const_len) + 4 * sizeof(long),
+              "the link's coefficients fill the lengths' place behind the weights: one aligned scalar load, sizeof(BatchArgs) unchanged");
 static_assert(sizeof(BigTheta) <= sizeof(MapTheta) * kMaxMaps, "the big tier's tables take the place of maps[]");
 constexpr size_t kArgsHeadBytes = offsetof(BatchArgs, maps);  // what the kernel keeps in LDS
 static_assert(kArgsHeadBytes % 16 == 0 && offsetof(BatchArgs, cur) % 8 == 0, "LDS copy of the argument block");
@@ -316,16 +325,18 @@ struct LaunchShape {
     bool taps;   // stencil model: the operator's weights are the launch's (BatchArgs::taps), not the built-in literals
     bool noise;  // stencil model: the launch carries the context's noise vectors (BatchArgs::consts[0 .. 1] = {omega, s}; models.hpp,
                  // SmoothNoiseModel) and its weights -- (1/2, 1/4) when none were set -- in BatchArgs::taps
+    bool link;   // stencil model: the launch carries the context's response coefficients as well (BatchArgs::link = {a2, a3}; models.hpp,
+                 // SmoothLinkModel), with noise vectors -- unit ones when none were set -- and weights as `noise` has them; map kernels only
     size_t lds;
     void* done_event;  // hipEvent_t (or null) that the launch itself signals on completion: no separate event packet
 };
 hipError_t launch_solver(const LaunchShape& s, const BatchArgs& a, hipStream_t stream);
-// (taps: the stencil model with the launch's own weights, BatchArgs::taps; noisy: with its own noise vectors as well)
-hipError_t launch_sample(int model, bool taps, bool noisy, const BatchArgs& a, uint64_t sim, double* x, double* z, double* noise, hipStream_t stream);
+// (taps: the stencil model with the launch's own weights, BatchArgs::taps; noisy: with its own noise vectors as well; link: and its response)
+hipError_t launch_sample(int model, bool taps, bool noisy, bool link, const BatchArgs& a, uint64_t sim, double* x, double* z, double* noise, hipStream_t stream);
 // the standard normals of ONE stream into a slot of the normals cache's layout ([2][ld]: n1, n2), drawn by the whole GPU instead of
 // by the one workgroup that solves the stream's problem (muse_engine.cpp, fd_values_impl: the fiducial MAP of get_H!)
 hipError_t launch_normals(uint64_t seed, uint64_t sim, int64_t ld, double* slot, hipStream_t stream);
-hipError_t launch_loglike(int model, bool taps, bool noise, const BatchArgs& a, const double* x, const double* z, double* g, double* out, hipStream_t stream);
+hipError_t launch_loglike(int model, bool taps, bool noise, bool link, const BatchArgs& a, const double* x, const double* z, double* g, double* out, hipStream_t stream);
 // the device-resident loop: false where the placement has no loop kernel (cluster placements); max_grid = the number of
 // workgroups that are certainly resident at once (they meet at the end of every iteration)
 bool loop_supported(const LaunchShape& s);

@@ -954,6 +954,9 @@ hipError_t loop_place(const LaunchShape& s, const LoopCall& c) {
 #define MUSE_INSTANTIATE_STENCIL(X, M)                                                              \
     X template hipError_t launch_place<M>(const LaunchShape&, const BatchArgs&, hipStream_t);       \
     X template hipError_t launch_place_implicit<M>(const LaunchShape&, const BatchArgs&, hipStream_t);
+// (the map kernels alone: a model whose implicit-differentiation pass the engine refuses, models.hpp, SmoothLinkModel)
+#define MUSE_INSTANTIATE_STENCIL_MAP(X, M) X template hipError_t launch_place<M>(const LaunchShape&, const BatchArgs&, hipStream_t);
+#define MUSE_INSTANTIATE_BIG_MAP(X, M) X template hipError_t launch_place_big<M>(const LaunchShape&, const BatchArgs&, hipStream_t);
 #define MUSE_INSTANTIATE_BIG(X, M)                                                                  \
     X template hipError_t launch_place_big<M>(const LaunchShape&, const BatchArgs&, hipStream_t);   \
     X template hipError_t launch_place_implicit<M>(const LaunchShape&, const BatchArgs&, hipStream_t);
@@ -1007,7 +1010,9 @@ hipError_t loop_place(const LaunchShape& s, const LoopCall& c) {
 #define MUSE_PART_6(X) MUSE_INSTANTIATE_STENCIL(X, SmoothModel<kMaxTheta>) MUSE_INSTANTIATE_BIG(X, SmoothModel<kBigTheta>) \
                        MUSE_INSTANTIATE_STENCIL(X, SmoothTapsModel<kMaxTheta>) MUSE_INSTANTIATE_BIG(X, SmoothTapsModel<kBigTheta>) \
                        MUSE_INSTANTIATE_STENCIL(X, SmoothNoiseModel<kMaxTheta>) MUSE_INSTANTIATE_BIG(X, SmoothNoiseModel<kBigTheta>)
-#define MUSE_PART_7(X) MUSE_INSTANTIATE_BIG(X, FunnelModel<kBigTheta>)
+#define MUSE_PART_7(X) MUSE_INSTANTIATE_BIG(X, FunnelModel<kBigTheta>) \
+                       MUSE_INSTANTIATE_STENCIL_MAP(X, SmoothLinkModel<2>) MUSE_INSTANTIATE_STENCIL_MAP(X, SmoothLinkModel<4>) \
+                       MUSE_INSTANTIATE_STENCIL_MAP(X, SmoothLinkModel<kMaxTheta>) MUSE_INSTANTIATE_BIG_MAP(X, SmoothLinkModel<kBigTheta>)
 #endif
 constexpr int kKernelParts = 8;
 }  // namespace muse

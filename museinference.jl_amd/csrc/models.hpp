@@ -67,6 +67,7 @@ struct SmoothModel {  // z as funnel, x = A z + n, A = periodic (1/4, 1/2, 1/4);
     static constexpr bool kStencil = true;
     static constexpr int kId = MUSE_MODEL_SMOOTH;
     static constexpr bool kNoise = false;   // unit noise variance, every element observed
+    static constexpr bool kLink = false;    // x = A z + n: no response function behind the operator
     __device__ static __forceinline__ double w0() { return 0.5; }
     __device__ static __forceinline__ double w1() { return 0.25; }
     __device__ static __forceinline__ double score_term(double, double z, int) { return z * z; }
@@ -84,6 +85,7 @@ struct SmoothTapsModel {
     static constexpr bool kStencil = true;
     static constexpr int kId = MUSE_MODEL_SMOOTH;
     static constexpr bool kNoise = false;
+    static constexpr bool kLink = false;
     __device__ static __forceinline__ double w0() { return ((kernarg_f64)__builtin_amdgcn_kernarg_segment_ptr())[offsetof(BatchArgs, taps) / 8]; }
     __device__ static __forceinline__ double w1() { return ((kernarg_f64)__builtin_amdgcn_kernarg_segment_ptr())[offsetof(BatchArgs, taps) / 8 + 1]; }
     __device__ static __forceinline__ double score_term(double, double z, int) { return z * z; }
@@ -104,6 +106,44 @@ struct SmoothNoiseModel : SmoothTapsModel<MAXB_> {
     }
     __device__ static __forceinline__ int64_t noise_ld() { return ((kernarg_i64)__builtin_amdgcn_kernarg_segment_ptr())[offsetof(BatchArgs, ld) / 8]; }
 };
+// ... and with a pointwise response behind the operator (muse_set_link): u = A z, x_i = phi(u_i) + s_i n2_i,
+// phi(u) = u + a2 u^2 + a3 u^3, -logLike = 1/2 sum_i omega_i r_i^2 + ..., r = x - phi(A z), grad_z = e^-theta z - A' (omega phi'(u) r).
+// The two coefficients are the launching context's, wavefront-uniform scalars read from the kernarg-only tail of the argument block
+// (BatchArgs::link, behind the weights in the place of the constants' lengths), so contexts with different links may have launches
+// in flight together.  phi enters through link_value, phi' through link_slope / link_rho below, each the identity (1) for every
+// model without a link.  Every expression is written so that at (a2, a3) = (0, 0) it rounds as SmoothNoiseModel's does:
+// fma(u h, u, u) with h = fma(a3, u, a2) = 0 is u, phi' = fma(u, fma(3 a3, u, 2 a2), 1) is 1, q 1 = q -- these kernels then give the
+// bits of the context without a link (for finite u: z is finite wherever the solver evaluates).
+template <int MAXB_>
+struct SmoothLinkModel : SmoothNoiseModel<MAXB_> {
+    static constexpr bool kLink = true;
+    __device__ static __forceinline__ double a2() { return ((kernarg_f64)__builtin_amdgcn_kernarg_segment_ptr())[offsetof(BatchArgs, link) / 8]; }
+    __device__ static __forceinline__ double a3() { return ((kernarg_f64)__builtin_amdgcn_kernarg_segment_ptr())[offsetof(BatchArgs, link) / 8 + 1]; }
+};
+template <class Model>
+constexpr bool link_model() {
+    if constexpr (Model::kStencil) return Model::kLink;
+    else return false;
+}
+// phi(u) = u + u^2 (a2 + a3 u): three rounded operations beside the load of the coefficients
+template <class Model>
+__device__ __forceinline__ double link_value(double u) {
+    if constexpr (link_model<Model>()) return fma(u * fma(Model::a3(), u, Model::a2()), u, u);
+    else return u;
+}
+// phi'(u) = 1 + u (2 a2 + 3 a3 u) (the two products of the coefficients are scalar work)
+template <class Model>
+__device__ __forceinline__ double link_slope(double u) {
+    if constexpr (link_model<Model>()) return fma(u, fma(3.0 * Model::a3(), u, 2.0 * Model::a2()), 1.0);
+    else return 1.0;
+}
+// rho = q phi'(u), the gradient's operand from the weighted residual q = omega r: gradient t - stencil_apply(rho_m, rho_0, rho_p);
+// the objective's share stays fma(t, z0, fma(q0, r0, facc)) -- q, not rho.  q itself for every model without a link.
+template <class Model>
+__device__ __forceinline__ double link_rho(double q, double u) {
+    if constexpr (link_model<Model>()) return q * link_slope<Model>(u);
+    else return q;
+}
 template <class Model>
 constexpr bool noise_model() {
     if constexpr (Model::kStencil) return Model::kNoise;

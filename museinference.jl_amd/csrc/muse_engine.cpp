@@ -119,6 +119,13 @@ struct muse_ctx {
     bool noise_on = false;
     double* noise_dev[2] = {nullptr, nullptr};   // {omega, s}
     std::vector<double> noise_sd, noise_mask;
+    // the stencil model's response phi(u) = u + a2 u^2 + a3 u^3 behind the operator (muse_set_link): the two coefficients travel in
+    // every launch's own argument block and select the kernels that apply them (models.hpp, SmoothLinkModel).  Those kernels read
+    // noise vectors and weights as well: a context with a link and no noise map points them at unit vectors of its own (link_unit:
+    // 1 where i < N, the pad element 0).  Never set, or set back with NULL: no link and the kernels without
+    bool link_on = false;
+    double link_a[2] = {0.0, 0.0};               // {a2, a3}
+    double* link_unit = nullptr;                 // [ld]: omega = s = 1
     bool nc_auto = true;                 // muse_set_normals_cache: plain maps may store / load the normals of repeated simulations
     double* fid_norm = nullptr;          // [2][ld]: the standard normals of get_H!'s fiducial stream, drawn by a kernel of its own (fd_values_impl)
     unsigned int* fid_flag = nullptr;    // device word: the tag of the last fiducial MAP published inside a finite-difference launch
@@ -444,6 +451,7 @@ static int launch_batch(muse_ctx* c, BatchArgs& a, hipEvent_t done = nullptr, bo
         shape.lds_s = !implicit && pl == P_C256 && stencil_lds_s(c, a.csize);
         shape.taps = c->stencil_taps;
         shape.noise = c->noise_on;
+        shape.link = c->link_on;
         shape.done_event = done;
         const hipError_t e = launch_solver(shape, a, c->lane->stream);
         if (e == hipErrorNotSupported && shape.jacobi)   // (kernels.hpp, launch_one: nothing was launched)
@@ -543,10 +551,14 @@ static void set_launch_constants(const muse_ctx* c, BatchArgs& a) {
         a.consts[k] = c->consts_dev[k];
         a.const_len[k] = c->consts_len[k];
     }
-    if (c->stencil_taps || c->noise_on)   // (the stencil model has no constants: the weights take the place of their lengths, args.hpp)
+    if (c->stencil_taps || c->noise_on || c->link_on)   // (the stencil model has no constants: the weights take the place of their lengths, args.hpp)
         for (int k = 0; k < kStencilWeights; ++k) a.taps[k] = c->stencil_w[k];
     if (c->noise_on)       // (... and the noise vectors the place of the first two pointers; the kernels with run-time noise read the
         for (int k = 0; k < 2; ++k) a.consts[k] = c->noise_dev[k];   // weights too: (1/2, 1/4), the built-in's bits, when none were set)
+    if (c->link_on) {      // (... the link's coefficients behind the weights, and unit noise vectors where the context has no noise map)
+        for (int k = 0; k < 2; ++k) a.link[k] = c->link_a[k];
+        if (!c->noise_on) a.consts[0] = a.consts[1] = c->link_unit;
+    }
 }
 
 extern "C" {
@@ -721,7 +733,7 @@ int muse_ctx_destroy(muse_ctx* c) {
         for (int k = 0; k < MUSE_MODEL_MAX_CONST; ++k) { muse_host_consts[k] = nullptr; muse_host_const_len[k] = 0; }
     }
 #endif
-    hipFree(c->noise_dev[0]); hipFree(c->noise_dev[1]);
+    hipFree(c->noise_dev[0]); hipFree(c->noise_dev[1]); hipFree(c->link_unit);
     hipFree(c->x_data); hipFree(c->fid_flag); hipFree(c->fid_norm); hipFree(c->tmp);
     hipFree(c->small_dev); if (c->tsample_dev) hipFree(c->tsample_dev); if (c->tsample_pin) hipHostFree(c->tsample_pin);
     if (c->comm_buf) hipFree(c->comm_buf);
@@ -933,6 +945,48 @@ int muse_get_noise(muse_ctx* c, double* sd_out, double* mask_out, int* runtime_o
         if (mask_out) mask_out[i] = c->noise_on ? c->noise_mask[(size_t)i] : 1.0;
     }
     if (runtime_out) *runtime_out = c->noise_on ? 1 : 0;
+    return MUSE_OK;
+}
+int muse_set_link(muse_ctx* c, const double* a) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+#ifdef MUSE_USER_MODEL_HEADER
+    (void)a;
+    return fail(MUSE_ERR_INVALID, "muse_set_link: this library was built from a user's model header and holds no stencil model");
+#else
+    if (c->model != MUSE_MODEL_SMOOTH) return fail(MUSE_ERR_INVALID, "muse_set_link: the context's model is not MUSE_MODEL_SMOOTH");
+    if (!a) {   // back to x = A z + noise and the kernels that ran before
+        c->link_on = false;
+        c->link_a[0] = c->link_a[1] = 0.0;
+        return MUSE_OK;
+    }
+    // (every check before anything of the context changes: a refused call leaves it as it was)
+    if (!isfinite(a[0]) || !isfinite(a[1])) return fail(MUSE_ERR_INVALID, "muse_set_link: the coefficients a2 and a3 must be finite");
+    if (!c->link_unit) {   // the unit noise vectors of a context with a link and no noise map: made once, never written again
+        std::vector<double> ones((size_t)c->ld, 0.0);   // (the pad element: 0)
+        for (int64_t i = 0; i < c->N; ++i) ones[(size_t)i] = 1.0;
+        double* fresh = nullptr;
+        hipError_t e = hipMalloc(&fresh, (size_t)c->ld * sizeof(double));
+        if (e == hipSuccess) e = hipMemcpy(fresh, ones.data(), (size_t)c->ld * sizeof(double), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            hipFree(fresh);
+            return fail(MUSE_ERR_HIP, std::string("muse_set_link: the unit noise vector: ") + hipGetErrorString(e));
+        }
+        c->link_unit = fresh;
+    }
+    // (nothing to wait for: a launch in flight carries its own copy of the coefficients)
+    c->link_a[0] = a[0];
+    c->link_a[1] = a[1];
+    c->link_on = true;
+    return MUSE_OK;
+#endif
+}
+int muse_get_link(muse_ctx* c, double* a_out, int* runtime_out) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (c->model != MUSE_MODEL_SMOOTH) return fail(MUSE_ERR_INVALID, "muse_get_link: the context's model is not MUSE_MODEL_SMOOTH");
+    if (a_out) { a_out[0] = c->link_a[0]; a_out[1] = c->link_a[1]; }
+    if (runtime_out) *runtime_out = c->link_on ? 1 : 0;
     return MUSE_OK;
 }
 int muse_set_constants(muse_ctx* c, int k, const double* values, int64_t count, int mem) {
@@ -1165,7 +1219,7 @@ int muse_sample_x_z(muse_ctx* c, uint64_t seed, int64_t sim, const double* theta
     base_args(c, a, theta);
     a.seed = seed;
     double *dx = c->tmp, *dz = c->tmp + c->ld, *dn = c->tmp + 2 * c->ld;
-    HIPCHK(launch_sample(c->model, c->stencil_taps, c->noise_on, a, (uint64_t)sim, dx, dz, dn, c->lane->stream));
+    HIPCHK(launch_sample(c->model, c->stencil_taps, c->noise_on, c->link_on, a, (uint64_t)sim, dx, dz, dn, c->lane->stream));
     if (x_out) HIPCHK(hipMemcpyAsync(x_out, dx, (size_t)c->N * sizeof(double), out_kind(mem), c->lane->stream));
     if (z_out) HIPCHK(hipMemcpyAsync(z_out, dz, (size_t)c->N * sizeof(double), out_kind(mem), c->lane->stream));
     HIPCHK(hipStreamSynchronize(c->lane->stream));
@@ -1178,7 +1232,7 @@ static int run_loglike(muse_ctx* c, const double* x, const double* z, const doub
     double *dx = c->tmp, *dz = c->tmp + c->ld;
     HIPCHK(hipMemcpyAsync(dx, x, (size_t)c->N * sizeof(double), in_kind(mem), c->lane->stream));
     HIPCHK(hipMemcpyAsync(dz, z, (size_t)c->N * sizeof(double), in_kind(mem), c->lane->stream));
-    HIPCHK(launch_loglike(c->model, c->stencil_taps, c->noise_on, a, dx, dz, gdev, c->small_dev, c->lane->stream));
+    HIPCHK(launch_loglike(c->model, c->stencil_taps, c->noise_on, c->link_on, a, dx, dz, gdev, c->small_dev, c->lane->stream));
     return MUSE_OK;
 }
 
@@ -1587,7 +1641,7 @@ static bool loop_usable(muse_ctx* c, int S, int64_t nlocal, LaunchShape* shape_o
     const int64_t nprob_total = (int64_t)S + 1;
     const int pl = choose_place(c);
     LaunchShape shape;
-    shape.model = c->model; shape.ntheta = nt; shape.place = pl; shape.grid = 0; shape.implicit = false; shape.jacobi = false; shape.lds_s = false; shape.taps = false; shape.noise = false;
+    shape.model = c->model; shape.ntheta = nt; shape.place = pl; shape.grid = 0; shape.implicit = false; shape.jacobi = false; shape.lds_s = false; shape.taps = false; shape.noise = false; shape.link = false;
     shape.big = false;  // (the loop kernel runs the resident placements)
     shape.done_event = nullptr;
     const bool xg_lds = pl == P_R512x10;
@@ -2129,10 +2183,16 @@ struct CgOptions {   // IterativeSolvers.cg's keywords and get_H!'s implicit_dif
     int flags;
 };
 static const double kCgReltolDefault = 1.4901161193847656e-08;   // sqrt(eps): what the default kernels of the other models compute themselves
+// (the sentence muse.py's get_H_(implicit_diff=True) raises with too, before any launch)
+static const char* const kLinkImplicitRefusal =
+    "the implicit-differentiation H is not available for a context with a link (muse_set_link): the Hessian in z is "
+    "A' diag(omega (phi'^2 - r phi'')) A + diag(e^-theta), and the r phi'' term can make it indefinite away from the MAP, where conjugate "
+    "gradients does not apply -- use the finite-difference entries";
 static int implicit_impl(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t e_begin, int64_t e_end, bool per_column,
                          const double* theta0, double atol, const CgOptions& cg, double* cols_out, int32_t* cg_iters_out) {
     const int nt = c->ntheta;
     const int64_t ne = e_end - e_begin;
+    if (c->link_on) return fail(MUSE_ERR_INVALID, kLinkImplicitRefusal);
     if (!muse_model_has_second())
         return fail(MUSE_ERR_INVALID, "the implicit-differentiation H needs second derivatives, which this model's header does not "
                                       "supply (MUSE_MODEL_SECOND or MUSE_MODEL_PAIR_SECOND, include/muse_model.h): use the finite-difference entries");

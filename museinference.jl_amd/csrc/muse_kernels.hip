@@ -134,6 +134,20 @@ __global__ void __launch_bounds__(256) smooth_finish_noise_kernel(BatchArgs a, c
     }
 }
 
+// (... and a response behind the operator, muse_set_link: x = phi(A z) + s n2, the coefficients the launch's, BatchArgs::link)
+__global__ void __launch_bounds__(256) smooth_finish_link_kernel(BatchArgs a, const double* __restrict__ z, const double* __restrict__ noise,
+                                                                 double* __restrict__ x) {
+    const int64_t N = a.N;
+    const double* __restrict__ sn = a.consts[1];
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t im = i == 0 ? N - 1 : i - 1, ip = i == N - 1 ? 0 : i + 1;
+        const double si = sn[i];
+        using M = SmoothLinkModel<kMaxTheta>;
+        const double xv = fma(si, noise[i], link_value<M>(stencil_apply<M>(z[im], z[i], z[ip])));
+        x[i] = si != 0.0 ? xv : 0.0;
+    }
+}
+
 // logLike and grad_z logLike (note the sign: the solver works with -logLike), plus the per-block score
 // sums; one workgroup, fixed-shape reduction (same element->thread map as the solver).
 template <class Model>
@@ -175,10 +189,24 @@ __global__ void __launch_bounds__(1024) loglike_kernel(BatchArgs a, const double
             const int ic = valid ? i : 0;
             const int im2 = wrap(ic - 2), im1 = wrap(ic - 1), ip1 = wrap(ic + 1), ip2 = wrap(ic + 2);
             const double zm2 = zin[im2], zm1 = zin[im1], z0 = zin[ic], zp1 = zin[ip1], zp2 = zin[ip2];
-            const double rm = xin[im1] - stencil_apply<Model>(zm2, zm1, z0);
-            const double r0 = xin[ic] - stencil_apply<Model>(zm1, z0, zp1);
-            const double rp = xin[ip1] - stencil_apply<Model>(z0, zp1, zp2);
+            // (u = A z and r = x - phi(u): link_value is the identity for every model without a link, models.hpp)
+            const double um = stencil_apply<Model>(zm2, zm1, z0);
+            const double rm = xin[im1] - link_value<Model>(um);
+            const double u0 = stencil_apply<Model>(zm1, z0, zp1);
+            const double r0 = xin[ic] - link_value<Model>(u0);
+            const double up = stencil_apply<Model>(z0, zp1, zp2);
+            const double rp = xin[ip1] - link_value<Model>(up);
             const double t = ivk * z0;
+            if constexpr (link_model<Model>()) {   // (the link's fork: the gradient's operands become rho = q phi'(u), models.hpp, link_rho)
+                const double* __restrict__ om = a.consts[0];
+                const double om_m = om[im1], om_0 = om[ic], om_p = om[ip1];
+                const double mm = noise_residual<Model>(om_m, rm), m0 = noise_residual<Model>(om_0, r0), mp = noise_residual<Model>(om_p, rp);
+                const double q0 = noise_weigh<Model>(om_0, m0);
+                const double pm = link_rho<Model>(noise_weigh<Model>(om_m, mm), um), p0 = link_rho<Model>(q0, u0);
+                const double pp = link_rho<Model>(noise_weigh<Model>(om_p, mp), up);
+                sum[0] = valid ? fma(t, z0, fma(q0, m0, sum[0])) : sum[0];
+                gi = valid ? t - stencil_apply<Model>(pm, p0, pp) : 0.0;
+            } else
             if constexpr (noise_model<Model>()) {   // (run-time noise: the weighted residuals, models.hpp, noise_weigh)
                 const double* __restrict__ om = a.consts[0];
                 // (a masked element's x may hold anything, NaN included: its residual is dropped before it is weighed)
@@ -279,6 +307,8 @@ hipError_t launch_solver(const LaunchShape& s, const BatchArgs& a, hipStream_t s
     if (s.big) {  // the big tier (args.hpp, BigTheta; muse_engine.cpp, tier_big): streaming placements only
         if (s.model == MUSE_MODEL_FUNNEL)
             return s.implicit ? launch_place_implicit<FunnelModel<kBigTheta>>(s, a, st) : launch_place_big<FunnelModel<kBigTheta>>(s, a, st);
+        if (s.model == MUSE_MODEL_SMOOTH && s.link)   // (map kernels only: muse_engine.cpp refuses the implicit pass of a context with a link)
+            return s.implicit ? hipErrorInvalidValue : launch_place_big<SmoothLinkModel<kBigTheta>>(s, a, st);
         if (s.model == MUSE_MODEL_SMOOTH && s.noise)
             return s.implicit ? launch_place_implicit<SmoothNoiseModel<kBigTheta>>(s, a, st) : launch_place_big<SmoothNoiseModel<kBigTheta>>(s, a, st);
         if (s.model == MUSE_MODEL_SMOOTH && s.taps)
@@ -294,6 +324,7 @@ hipError_t launch_solver(const LaunchShape& s, const BatchArgs& a, hipStream_t s
                    : nt == 2 ? launch_place_implicit<FunnelModel<2>>(s, a, st)
                    : nt <= 4 ? launch_place_implicit<FunnelModel<4>>(s, a, st)
                              : launch_place_implicit<FunnelModel<kMaxTheta>>(s, a, st);
+        if (s.link) return hipErrorInvalidValue;   // (muse_engine.cpp refuses the call before it gets here)
         if (s.noise)
             return nt <= 2   ? launch_place_implicit<SmoothNoiseModel<2>>(s, a, st)
                    : nt <= 4 ? launch_place_implicit<SmoothNoiseModel<4>>(s, a, st)
@@ -312,6 +343,10 @@ hipError_t launch_solver(const LaunchShape& s, const BatchArgs& a, hipStream_t s
                : nt == 2 ? launch_place<FunnelModel<2>>(s, a, st)
                : nt <= 4 ? launch_place<FunnelModel<4>>(s, a, st)
                          : launch_place<FunnelModel<kMaxTheta>>(s, a, st);
+    if (s.link)
+        return nt <= 2   ? launch_place<SmoothLinkModel<2>>(s, a, st)
+               : nt <= 4 ? launch_place<SmoothLinkModel<4>>(s, a, st)
+                         : launch_place<SmoothLinkModel<kMaxTheta>>(s, a, st);
     if (s.noise)
         return nt <= 2   ? launch_place<SmoothNoiseModel<2>>(s, a, st)
                : nt <= 4 ? launch_place<SmoothNoiseModel<4>>(s, a, st)
@@ -441,11 +476,11 @@ hipError_t launch_normals(uint64_t seed, uint64_t sim, int64_t ld, double* slot,
     return hipGetLastError();
 }
 
-hipError_t launch_sample(int model, bool taps, bool noisy, const BatchArgs& a, uint64_t sim, double* x, double* z, double* noise, hipStream_t st) {
+hipError_t launch_sample(int model, bool taps, bool noisy, bool link, const BatchArgs& a, uint64_t sim, double* x, double* z, double* noise, hipStream_t st) {
     const int grid = (int)((a.N + 255) / 256 < 4096 ? (a.N + 255) / 256 : 4096);
 #ifdef MUSE_USER_MODEL_HEADER
     (void)noise;
-    if (model != MUSE_MODEL_USER || taps || noisy) return hipErrorInvalidValue;
+    if (model != MUSE_MODEL_USER || taps || noisy || link) return hipErrorInvalidValue;
     hipLaunchKernelGGL(sample_user_kernel, dim3(grid), dim3(256), 0, st, a, sim, x, z);
     return hipGetLastError();
 #endif
@@ -453,16 +488,17 @@ hipError_t launch_sample(int model, bool taps, bool noisy, const BatchArgs& a, u
     else if (model == MUSE_MODEL_FUNNEL) hipLaunchKernelGGL(sample_kernel<MUSE_MODEL_FUNNEL>, dim3(grid), dim3(256), 0, st, a, sim, x, z);
     else {
         hipLaunchKernelGGL(sample_kernel<MUSE_MODEL_SMOOTH>, dim3(grid), dim3(256), 0, st, a, sim, noise, z);
-        if (noisy) hipLaunchKernelGGL(smooth_finish_noise_kernel, dim3(grid), dim3(256), 0, st, a, z, noise, x);
+        if (link) hipLaunchKernelGGL(smooth_finish_link_kernel, dim3(grid), dim3(256), 0, st, a, z, noise, x);
+        else if (noisy) hipLaunchKernelGGL(smooth_finish_noise_kernel, dim3(grid), dim3(256), 0, st, a, z, noise, x);
         else if (taps) hipLaunchKernelGGL(smooth_finish_taps_kernel, dim3(grid), dim3(256), 0, st, a, z, noise, x);
         else hipLaunchKernelGGL(smooth_finish_kernel, dim3(grid), dim3(256), 0, st, a.N, z, noise, x);
     }
     return hipGetLastError();
 }
 
-hipError_t launch_loglike(int model, bool taps, bool noise, const BatchArgs& a, const double* x, const double* z, double* g, double* out, hipStream_t st) {
+hipError_t launch_loglike(int model, bool taps, bool noise, bool link, const BatchArgs& a, const double* x, const double* z, double* g, double* out, hipStream_t st) {
 #ifdef MUSE_USER_MODEL_HEADER
-    if (model != MUSE_MODEL_USER || taps || noise) return hipErrorInvalidValue;
+    if (model != MUSE_MODEL_USER || taps || noise || link) return hipErrorInvalidValue;
 #ifdef MUSE_MODEL_PAIR
     if (a.ntheta > kMaxTheta) return hipErrorInvalidValue;
 #else
@@ -475,6 +511,8 @@ hipError_t launch_loglike(int model, bool taps, bool noise, const BatchArgs& a, 
     if (model == MUSE_MODEL_NOISE) hipLaunchKernelGGL(loglike_kernel<NoiseModel>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
     else if (model == MUSE_MODEL_FUNNEL && a.ntheta > kMaxTheta) hipLaunchKernelGGL(loglike_kernel<FunnelModel<kBigTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
     else if (model == MUSE_MODEL_FUNNEL) hipLaunchKernelGGL(loglike_kernel<FunnelModel<kMaxTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
+    else if (link && a.ntheta > kMaxTheta) hipLaunchKernelGGL(loglike_kernel<SmoothLinkModel<kBigTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
+    else if (link) hipLaunchKernelGGL(loglike_kernel<SmoothLinkModel<kMaxTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
     else if (noise && a.ntheta > kMaxTheta) hipLaunchKernelGGL(loglike_kernel<SmoothNoiseModel<kBigTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
     else if (noise) hipLaunchKernelGGL(loglike_kernel<SmoothNoiseModel<kMaxTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
     else if (taps && a.ntheta > kMaxTheta) hipLaunchKernelGGL(loglike_kernel<SmoothTapsModel<kBigTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);

@@ -406,6 +406,32 @@ struct Solver : PairState<Model::kPair> {
         q_out = q0;
         return t - stencil_apply<Model>(qm, q0, qp);
     }
+    // (a response behind the operator, models.hpp, SmoothLinkModel: r = x - phi(u), u = A z, and the gradient's operands
+    //  rho = q phi'(u) -- gradient t - A (omega phi'(u) r); the element's share stays fma(t, z0, fma(q0, r0, .)).  A function of its
+    //  own, as the one above is)
+    template <class ZT, class OM>
+    __device__ __forceinline__ double stencil_grad_linked(ZT&& zt, const OM& om, int i, double& t_out, double& z_out, double& r_out,
+                                                          double& q_out) const {
+        const int N = (int)a.N;
+        auto wrap = [&](int k) { return k < 0 ? k + N : (k >= N ? k - N : k); };
+        const int im2 = wrap(i - 2), im1 = wrap(i - 1), ip1 = wrap(i + 1), ip2 = wrap(i + 2);
+        const double zm2 = zt(im2), zm1 = zt(im1), z0 = zt(i), zp1 = zt(ip1), zp2 = zt(ip2);
+        const double om_m = om.get1(im1), om_0 = om.get1(i), om_p = om.get1(ip1);
+        const double um = stencil_apply<Model>(zm2, zm1, z0), u0 = stencil_apply<Model>(zm1, z0, zp1), up = stencil_apply<Model>(z0, zp1, zp2);
+        // (a masked element's x may hold anything, NaN included: its residual is dropped before it is weighed, models.hpp)
+        const double rm = noise_residual<Model>(om_m, x.get1(im1) - link_value<Model>(um));
+        const double r0 = noise_residual<Model>(om_0, x.get1(i) - link_value<Model>(u0));
+        const double rp = noise_residual<Model>(om_p, x.get1(ip1) - link_value<Model>(up));
+        const double q0 = noise_weigh<Model>(om_0, r0);
+        const double pm = link_rho<Model>(noise_weigh<Model>(om_m, rm), um), p0 = link_rho<Model>(q0, u0);
+        const double pp = link_rho<Model>(noise_weigh<Model>(om_p, rp), up);
+        const double t = this->ivk(0, i) * z0;
+        t_out = t;
+        z_out = z0;
+        r_out = r0;
+        q_out = q0;
+        return t - stencil_apply<Model>(pm, p0, pp);
+    }
 
     // ---- stencil model, pair-wise --------------------------------------------------------------
     // A lane loads its own element pair of z, s, x with one 16-byte buffer instruction each and gets the
@@ -516,6 +542,30 @@ struct Solver : PairState<Model::kPair> {
                     rr[u][0] = noise_residual<Model>(wp.a, r0);
                     rr[u][1] = noise_residual<Model>(wp.b, r1);
                 }
+                // The link's fork (models.hpp, SmoothLinkModel) stands BEHIND the lines above and replaces what they left in g0, g1, qq and
+                // rr -- for this model they are dead code, which the compiler drops -- so that not one statement the kernels without a
+                // link are compiled from is touched, not even by a wrapper that would be the identity for them (tried first: the
+                // residuals above as x - link_value(u) gave the same arithmetic and another register allocation in 48 of the parent's
+                // kernels).  u = A z at the four places, r = x - phi(u), the noise fork's lines with the operands rho = q phi'(u); the
+                // objective's share keeps q.  An edit to the noise fork goes in here too, and into stencil_grad_linked.
+                if constexpr (link_model<Model>()) {
+                    const double um = stencil_apply<Model>(ztL.a, ztL.b, ztp.a), u0 = stencil_apply<Model>(ztL.b, ztp.a, ztp.b);
+                    const double u1 = stencil_apply<Model>(ztp.a, ztp.b, ztR.a), u2 = stencil_apply<Model>(ztp.b, ztR.a, ztR.b);
+                    double wL = dpp_move<kDppWaveShr1>(wp.b), wR = dpp_move<kDppWaveShl1>(wp.a);
+                    if (lane == 0) wL = we;
+                    if (lane == 63) wR = we;
+                    const double mm = noise_residual<Model>(wL, xL - link_value<Model>(um));
+                    const double m0 = noise_residual<Model>(wp.a, xp.a - link_value<Model>(u0));
+                    const double m1 = noise_residual<Model>(wp.b, xp.b - link_value<Model>(u1));
+                    const double m2 = noise_residual<Model>(wR, xR - link_value<Model>(u2));
+                    const double q0 = noise_weigh<Model>(wp.a, m0), q1 = noise_weigh<Model>(wp.b, m1);
+                    const double pm = link_rho<Model>(noise_weigh<Model>(wL, mm), um), p0 = link_rho<Model>(q0, u0);
+                    const double p1 = link_rho<Model>(q1, u1), p2 = link_rho<Model>(noise_weigh<Model>(wR, m2), u2);
+                    g0[u] = t0 - stencil_apply<Model>(pm, p0, p1);
+                    g1[u] = t1 - stencil_apply<Model>(p0, p1, p2);
+                    qq[u][0] = q0; qq[u][1] = q1;
+                    rr[u][0] = m0; rr[u][1] = m1;
+                }
             }
             // wrap-around, pad and out-of-range pairs: element-wise with modular neighbour indices
 #pragma unroll
@@ -526,6 +576,11 @@ struct Solver : PairState<Model::kPair> {
                     for (int v = 0; v < 2; ++v) {
                         const int i = i0 + v;
                         double gt = 0.0, t_ = 0.0, z_ = 0.0, r_ = 0.0;
+                        if constexpr (link_model<Model>()) {
+                            double q_ = 0.0;
+                            if (i < N) gt = stencil_grad_linked(ztf, om, i, t_, z_, r_, q_);
+                            qq[u][v] = q_;
+                        } else
                         if constexpr (noise_model<Model>()) {
                             double q_ = 0.0;
                             if (i < N) gt = stencil_grad_weighed(ztf, om, i, t_, z_, r_, q_);
@@ -1676,6 +1731,11 @@ struct Solver : PairState<Model::kPair> {
                     const int im = ic == 0 ? (int)N - 1 : ic - 1, ip = ic == (int)N - 1 ? 0 : ic + 1;
                     const double zl = g.get1(im), zr = g.get1(ip);
                     const double az = stencil_apply<Model>(zl, g.get1(ic), zr);
+                    if constexpr (link_model<Model>()) {   // (a response behind the operator: x = phi(A z) + s n2, 0 where masked)
+                        const double si = sn.get(jj, i);
+                        const double xv = fma(si, x.get(jj, i), link_value<Model>(az));
+                        x.set(jj, i, valid && si != 0.0 ? xv : 0.0);
+                    } else
                     if constexpr (noise_model<Model>()) {
                         const double si = sn.get(jj, i);
                         const double xv = fma(si, x.get(jj, i), az);

@@ -155,6 +155,14 @@ class ShardedMuseProblem:
     def get_noise(self):
         return self.local.get_noise()
 
+    def set_link(self, link):
+        """The "smooth" model's response coefficients (HipMuseProblem.set_link) on this rank's problem: every rank calls it with the
+        same pair."""
+        return self.local.set_link(link)
+
+    def get_link(self):
+        return self.local.get_link()
+
     # -- the muse! outer loop in the library's native code, sharded (muse_run_sharded of the C ABI): with the engine's own
     #    communicator every rank runs the loop itself -- one gathered map per iteration, the same step on every rank --
     #    and no Python, torch tensor or allocation sits between two maps.  Without it muse_() drives the maps from Python.

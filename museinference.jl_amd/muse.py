@@ -482,6 +482,10 @@ def _get_H_implicit(result, prob, theta0, rng, nsims, cg_kwargs, skip_errors, H1
     (src/muse.jl:353); the fiducial MAP is solved to 1e-1 as the reference hard-codes (src/muse.jl:344).  CG iteration counts go to
     metadata["implicit_diff_cg_hists"].  A keyword beyond atol and cg_maxiter reaches the problem only when it is given, so that a
     problem whose seam does not know it says so instead of ignoring it."""
+    refusal = getattr(prob, "implicit_diff_refusal", None)   # (a problem that knows it cannot: said before any launch)
+    reason = refusal() if callable(refusal) else None
+    if reason:
+        raise _capi.MuseError(-1, reason)   # (MUSE_ERR_INVALID: what muse_implicit_H_* itself returns for it)
     cg = _cg_keywords(cg_kwargs)
     if "cg_Pl" in cg and not _seam_takes(prob, "cg_Pl"):
         raise ValueError('implicit_diff_cg_kwargs: Pl must be the identity (None or an identity matrix) for this problem: "jacobi" needs '

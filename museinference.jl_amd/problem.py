@@ -173,6 +173,12 @@ def check_optim_soln(info, where="MAP"):
                                                  "for %d element(s).", where, int(nf.sum()))
 
 
+# (the engine's own sentence, muse_engine.cpp: muse_implicit_H_* of a context with a link)
+LINK_IMPLICIT_REFUSAL = ("the implicit-differentiation H is not available for a context with a link (muse_set_link): the Hessian in z is "
+                         "A' diag(omega (phi'^2 - r phi'')) A + diag(e^-theta), and the r phi'' term can make it indefinite away from the MAP, "
+                         "where conjugate gradients does not apply -- use the finite-difference entries")
+
+
 class HipMuseProblem(AbstractMuseProblem):
     """An AbstractMuseProblem whose operators run on one MI355X through libmuse_hip.so.
 
@@ -185,8 +191,10 @@ class HipMuseProblem(AbstractMuseProblem):
     supports_native_muse = True  # muse_() may hand the whole outer loop to muse_run (class attribute: wrappers
                                  # that forward attribute access to a HipMuseProblem do not inherit it)
 
-    def __init__(self, x, model="funnel", ntheta=1, prior=None, device=0, N=None, constants=None, stencil=None, noise_sd=None, mask=None):
-        """noise_sd, mask: -- model="smooth" only -- a noise standard deviation per element (N finite doubles > 0; a scalar is
+    def __init__(self, x, model="funnel", ntheta=1, prior=None, device=0, N=None, constants=None, stencil=None, noise_sd=None, mask=None, link=None):
+        """link: (a2, a3) -- model="smooth" only -- a pointwise response behind the operator, x_i = phi((A z)_i) + sd_i n_i with
+        phi(u) = u + a2 u^2 + a3 u^3; set_link changes it later.
+        noise_sd, mask: -- model="smooth" only -- a noise standard deviation per element (N finite doubles > 0; a scalar is
         broadcast) and which elements were observed (N of True / False, None: all): x_i = (A z)_i + sd_i n_i, masked elements enter
         nothing; set_noise changes them later.
         stencil: (w0, w1) -- model="smooth" only -- the weights of the operator (A z)_i = w1 (z_{i-1} + z_{i+1}) + w0 z_i in place
@@ -223,6 +231,8 @@ class HipMuseProblem(AbstractMuseProblem):
                 self.set_stencil(stencil)
             if noise_sd is not None or mask is not None:
                 self.set_noise(np.ones(self.N) if noise_sd is None else noise_sd, mask)
+            if link is not None:
+                self.set_link(link)
         except Exception:
             self.close()        # (a refused option: the context that was just created does not outlive the error)
             raise
@@ -265,6 +275,34 @@ class HipMuseProblem(AbstractMuseProblem):
         sd, m, rt = np.empty(self.N), np.empty(self.N), C.c_int()
         self._check(self._lib.muse_get_noise(self._ctx, _capi.ptr(sd), _capi.ptr(m), C.byref(rt)))
         return sd, m != 0.0, bool(rt.value)
+
+    def set_link(self, link):
+        """A pointwise response behind the operator of the "smooth" model as context state (muse_set_link): link = (a2, a3), any
+        finite pair, for x_i = phi(u_i) + sd_i n_i, u = A z, phi(u) = u + a2 u^2 + a3 u^3 -- gain compression, a quadratic or cubic
+        detector non-linearity -- with the problem's stencil, noise map and mask.  -logLike weighs r = x - phi(A z); its gradient in z
+        is e^-theta z - A' (omega phi'(u) r); the score is unchanged.  phi is strictly increasing for a2^2 < 3 a3; a response that
+        is not monotone makes the posterior in z multi-modal, and which mode a MAP finds is then the caller's business.  Every
+        operator, map, finite-difference get_H! and muse() of this problem uses it from the next call on; the implicit-
+        differentiation get_H! is refused while a link is set (LINK_IMPLICIT_REFUSAL).  link = None: no link and the kernels that
+        ran before; (0, 0) gives those kernels' results bit for bit."""
+        if link is None:
+            self._check(self._lib.muse_set_link(self._ctx, None))
+            return
+        a = _capi.f8(link, 2)
+        self._check(self._lib.muse_set_link(self._ctx, _capi.ptr(a)))
+
+    def get_link(self):
+        """((a2, a3), runtime): the response's coefficients -- (0, 0) without -- and whether the launches apply a link (False: the
+        kernels without run)."""
+        a, rt = np.empty(2), C.c_int()
+        self._check(self._lib.muse_get_link(self._ctx, _capi.ptr(a), C.byref(rt)))
+        return (float(a[0]), float(a[1])), bool(rt.value)
+
+    def implicit_diff_refusal(self):
+        """Why get_H_(implicit_diff=True) cannot run for this problem, or None: asked before anything is launched."""
+        if self.model == "smooth" and self.get_link()[1]:
+            return LINK_IMPLICIT_REFUSAL
+        return None
 
     def get_stencil(self):
         """((w0, w1), runtime): the operator's weights and whether they were set (False: the built-in stencil's kernels run)."""
