@@ -181,8 +181,15 @@ int muse_get_noise(muse_ctx* ctx, double* sd_out, double* mask_out, int* runtime
  * a == NULL: no link, AND the kernels the context launched before.
  * The implicit-differentiation get_H! (muse_implicit_H_*) of a context with a link is refused with MUSE_ERR_INVALID: the Hessian is
  * A' diag(omega (phi'^2 - r phi'')) A + diag(e^-theta), which the r phi'' term can make indefinite away from the MAP.
- * MUSE_ERR_INVALID: another model, a library built from a user's model header, a coefficient that is not finite -- the context keeps
- * the link it had. */
+ * MUSE_ERR_INVALID: another model, a library built from a user's ELEMENTWISE model header, a coefficient that is not finite -- the
+ * context keeps the link it had.
+ * A library built from a RESPONSE header (include/muse_model.h, MUSE_MODEL_RESPONSE: the stencil model with the header's phi, under
+ * MUSE_MODEL_USER) takes muse_set_stencil, muse_set_noise and this call as MUSE_MODEL_SMOOTH does: a = {p0, p1}, the two run-time
+ * numbers the header's functions receive; NULL means {0, 0}; numbers at which the header is not finite at u = 0 are refused, as
+ * muse_ctx_create refuses a header that is not finite there at {0, 0}.  Every launch of such a context carries the numbers, the weights
+ * ((1/2, 1/4) when none were set) and noise vectors (unit vectors when no map was set): muse_get_link always reports runtime 1.
+ * muse_set_placement(1) and muse_set_constants are refused; the implicit-differentiation get_H! runs for a header that states phi''
+ * (below). */
 int muse_set_link(muse_ctx* ctx, const double* a /* {a2, a3}, or NULL: no link and the kernels without */);
 /* The link in use: a_out[2] = {a2, a3} ({0, 0} without), *runtime_out = 1 when the launches apply a link and 0 for the kernels
  * without; either pointer may be NULL.  MUSE_ERR_INVALID for another model. */
@@ -196,7 +203,8 @@ int muse_get_link(muse_ctx* ctx, double* a_out, int* runtime_out);
  * block's two PARAMETERS a, b, and out[12] = { muse_model_grad, the objective term, t0 of muse_model_score_terms, the four
  * coefficients of muse_model_coefs(a, b), z, x of muse_model_sample, the block's constant C(a, b), t1, 0 }.  The model's run-time
  * constants are the context's; a model without them needs no context (ctx may be NULL, and no GPU is touched).  Built-in models:
- * MUSE_ERR_INVALID. */
+ * MUSE_ERR_INVALID.  A response header (MUSE_MODEL_RESPONSE, include/muse_model.h): `iv` and `sd` are the response's numbers p0, p1
+ * and `x` is u; out[10] = { phi(u; p), phi'(u; p), phi''(u; p) (NaN without MUSE_MODEL_RESPONSE_SECOND), 0 ... }; ctx may be NULL. */
 int muse_model_eval(muse_ctx* ctx, double iv, double sd, double x, double z, double n1, double n2, int64_t i, double* out);
 /* The second derivatives of a header of the two-parameter family that states them (MUSE_MODEL_PAIR_SECOND, include/muse_model.h),
  * on the host for one element of a block with parameters a, b: out[8] = { ozz, ozx, gza, gzb, sxa, sxb of muse_model_pair_second
@@ -204,7 +212,8 @@ int muse_model_eval(muse_ctx* ctx, double iv, double sd, double x, double z, dou
  * muse_model_eval (NULL when the model has no run-time constants).  Every other library: MUSE_ERR_INVALID. */
 int muse_model_eval_pair_second(muse_ctx* ctx, double a, double b, double x, double z, double n1, double n2, int64_t i, double* out);
 /* 1 when the library's model supplies second derivatives (the built-in models; a user header with MUSE_MODEL_SECOND or, in the
- * two-parameter family, MUSE_MODEL_PAIR_SECOND), i.e. when muse_implicit_H_* accept it; 0 otherwise. */
+ * two-parameter family, MUSE_MODEL_PAIR_SECOND, or a response header with MUSE_MODEL_RESPONSE_SECOND), i.e. when muse_implicit_H_*
+ * accept it; 0 otherwise. */
 int muse_model_has_second(void);
 /* The normals cache of plain maps.  A simulation's stream depends only on (seed, simulation index) (split_rng,
  * src/util.jl:87-92), and the reference's loops draw the same streams again and again -- every iteration of muse!
@@ -388,7 +397,14 @@ int muse_fd_values_columns(muse_ctx* ctx, uint64_t seed, int64_t sim_begin, int6
  *   header's muse_model_second / muse_model_dx_dsd -- in the two-parameter family muse_model_pair_second / muse_model_pair_dx --
  *   (include/muse_model.h; a header without them is refused).
  * Hs_out [nsims][ntheta][ntheta] host; cg_iters_out [nsims][ntheta] host (may be NULL; the
- * metadata[:implicit_diff_cg_hists] of src/muse.jl:405). */
+ * metadata[:implicit_diff_cg_hists] of src/muse.jl:405).
+ * A library built from a response header with MUSE_MODEL_RESPONSE_SECOND (include/muse_model.h): the Hessian applied is
+ * -[A' diag(d) A + diag(e^-theta)], d_i = omega_i (phi'(u_i)^2 - r_i phi''(u_i)), the right-hand side A' (omega phi'(u) phi'(u_t) A (z_true/2)|_j),
+ * H1 = 0.  It is definite at a MAP but need not be at the point a loose `atol` stops at, so conjugate gradients looks at p.Ap in every
+ * iteration: when that is not finite and of the definite sign the column stops there and its entry of cg_iters_out is NEGATIVE,
+ * -1 - (the iterations completed); H's column is then what the iterations so far gave and is not to be used -- solve with a tighter
+ * atol, or take the finite-difference entries.  The kernels of this family read cg_reltol, cg_abstol, cg_maxiter (0 included) and
+ * MUSE_IMPLICIT_H1_IS_ZERO (H1 is zero anyway) at run time; MUSE_IMPLICIT_PL_JACOBI is refused as for the stencil model. */
 int muse_implicit_H_batch(muse_ctx* ctx, uint64_t seed, int64_t sim_begin, int64_t sim_end, const double* theta0,
                           double atol, int cg_maxiter, double* Hs_out, int32_t* cg_iters_out);
 /* ... and over a range of columns of the same list (see muse_fd_jacobian_columns): cols_out [n][ntheta],

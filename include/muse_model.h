@@ -134,6 +134,31 @@
  * xb = 1/2 sd n1; models/normal_mean_var.h itself states none and runs get_H! by finite differences.)
  * museinference_jl_amd.ElementwiseModel.from_pair_expressions writes both functions from the model's terms; muse_model_eval_pair_second
  * of muse_hip.h evaluates them on the host, which is what check_model_consistency differentiates numerically.
+ *
+ * A RESPONSE BEHIND THE STENCIL OPERATOR (the coupled family).  The three families above are elementwise.  A header that says
+ *     #define MUSE_MODEL_RESPONSE 1                    (before including this file)
+ * states instead the pointwise response of the coupled stencil model (MUSE_MODEL_SMOOTH of muse_hip.h with run-time weights, noise
+ * map and mask):  z_i ~ N(0, e^theta_k),  u = A z the periodic (w1, w0, w1) stencil,
+ *     x_i = phi(u_i; p) + sd_i n_i   where the element is observed,
+ * and the whole of the header is
+ *     #define MUSE_MODEL_NAME "saturating_response"
+ *     MUSE_MODEL_FN void   muse_model_response(double u, const double* p, double* phi, double* dphi);
+ *         *phi = phi(u; p) and *dphi = d phi / d u from ONE function, so that the two may share sub-expressions; p[0] and p[1] are
+ *         two run-time numbers of the context (muse_set_link of muse_hip.h; (0, 0) until they are set), uniform over a launch
+ *     #define MUSE_MODEL_RESPONSE_SECOND 1             (optional)
+ *     MUSE_MODEL_FN double muse_model_response_second(double u, const double* p);
+ *         d2 phi / d u2: what the implicit-differentiation get_H! of this family needs (muse_model_has_second() = 1 with it; without
+ *         it the implicit entries refuse the library and get_H! runs by finite differences)
+ * under the rules of every family: plain C, doubles only, IEEE + - * / sqrt fma only, finite for every finite u -- u = 0 included,
+ * which the engine evaluates on the host when a context is created.  There is no element index: what varies per element travels in
+ * x, in the noise map and in the mask (muse_set_noise).  -logLike = 1/2 sum_i omega_i (x_i - phi(u_i))^2 + 1/2 sum_i e^-theta_k z_i^2 +
+ * 1/2 sum_k n_k theta_k; its gradient in z is e^-theta z - A' (omega phi'(u) r); the score is the stencil model's.  The family cannot
+ * be combined with MUSE_MODEL_PAIR or MUSE_MODEL_NCONST: the constant slots of a launch carry the noise vectors.  Such a library
+ * holds the model under MUSE_MODEL_USER, runs in the streaming and cluster placements as MUSE_MODEL_SMOOTH does, takes
+ * muse_set_stencil / muse_set_noise / muse_set_link, and muse_model_eval reads (iv, sd) as (p[0], p[1]) and x as u:
+ * out[0..2] = phi, phi', phi'' (NaN without MUSE_MODEL_RESPONSE_SECOND), zeros behind.  models/poly_response.h (the cubic of
+ * muse_set_link, in its expressions: the built-in link's bits) and models/saturating_response.h (u / sqrt(1 + (p0 u)^2)) are the
+ * shipped members; museinference_jl_amd.ResponseModel.from_expression writes phi' and phi'' from phi.
  */
 #ifndef MUSE_MODEL_H
 #define MUSE_MODEL_H
@@ -141,6 +166,14 @@
 #define MUSE_MODEL_FN static inline
 #endif
 #define MUSE_MODEL_MAX_CONST 4
+#ifdef MUSE_MODEL_RESPONSE
+#ifdef MUSE_MODEL_PAIR
+#error "MUSE_MODEL_RESPONSE cannot be combined with MUSE_MODEL_PAIR: the response family is the stencil model's, one parameter per block"
+#endif
+#ifdef MUSE_MODEL_NCONST
+#error "MUSE_MODEL_RESPONSE cannot be combined with MUSE_MODEL_NCONST: the constant slots of a launch carry the stencil model's noise vectors"
+#endif
+#endif
 #ifndef muse_model_exp
 /* The exponential a header of the two-parameter family forms its coefficients with.  The engine and its CPU checker define it
  * before they include the header -- one fixed sequence of IEEE operations, the same bits on host, device and checker; a plain

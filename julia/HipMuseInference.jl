@@ -273,6 +273,8 @@ end
 # x_i = phi((A z)_i) + sd_i n_i, phi(u) = u + a2 u^2 + a3 u^3, any finite pair -- used by every operator, map and finite-difference
 # get_H! from the next call on (the implicit-differentiation branch is refused while a link is set); `nothing`: no link and the
 # kernels that ran before.
+# (a library built from a response header -- include/muse_model.h, MUSE_MODEL_RESPONSE -- takes the same call: a = (p0, p1), the
+#  header's two run-time numbers; `nothing` means (0, 0))
 set_link(prob::HipMuseProblem, a::Union{Nothing,NTuple{2,Real}}) =
     check(ccall((:muse_set_link, libmuse_hip), Cint, (Ptr{Cvoid}, Ptr{Float64}), prob.ctx,
                 a === nothing ? C_NULL : Float64[a[1], a[2]]))

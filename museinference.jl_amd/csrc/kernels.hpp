@@ -131,6 +131,7 @@ map_score_kernel(const BatchArgs /*read via the kernarg segment*/) {
             wg_barrier<!Model::kStencil>();
             load_problem_theta<!Model::kStencil>(a, args_lds, p, tid);
             if constexpr (IMPLICIT && Model::kPair) sv.template run_implicit_pair<JACOBI>(p, cl_scratch, lds_x, lds_g);
+            else if constexpr (IMPLICIT && response_model<Model>()) sv.run_implicit_response(p, cl_scratch, lds_x, lds_g);
             else if constexpr (IMPLICIT) sv.template run_implicit<JACOBI>(p, cl_scratch, lds_x, lds_g);
             else sv.run(p, cl_scratch, lds_x, lds_g);
         }
@@ -168,6 +169,7 @@ map_score_kernel(const BatchArgs /*read via the kernarg segment*/) {
                 sv.pk[0] = pk0;
                 sv.pk[1] = pk1;
                 if constexpr (IMPLICIT && Model::kPair) sv.template run_implicit_pair<JACOBI>(p, wg_scratch, lds_x, lds_g);
+                else if constexpr (IMPLICIT && response_model<Model>()) sv.run_implicit_response(p, wg_scratch, lds_x, lds_g);
                 else if constexpr (IMPLICIT) sv.template run_implicit<JACOBI>(p, wg_scratch, lds_x, lds_g);
                 else sv.run(p, wg_scratch, lds_x, lds_g);
             }
@@ -960,9 +962,28 @@ hipError_t loop_place(const LaunchShape& s, const LoopCall& c) {
 #define MUSE_INSTANTIATE_BIG(X, M)                                                                  \
     X template hipError_t launch_place_big<M>(const LaunchShape&, const BatchArgs&, hipStream_t);   \
     X template hipError_t launch_place_implicit<M>(const LaunchShape&, const BatchArgs&, hipStream_t);
-#ifdef MUSE_USER_MODEL_HEADER
+#if defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_RESPONSE)
+// A response behind the stencil operator (include/muse_model.h, MUSE_MODEL_RESPONSE): the map kernels the link model has -- the
+// streaming and cluster placements in the tiers of 2, 4 and 8 components, the big tier -- and, for a header that states phi''
+// (MUSE_MODEL_RESPONSE_SECOND), the implicit differentiation's (solver.hpp, run_implicit_response).  No loop kernels: the stencil streams.
+#ifdef MUSE_MODEL_RESPONSE_SECOND
+#define MUSE_INSTANTIATE_RESPONSE(X, M) MUSE_INSTANTIATE_STENCIL(X, M)
+#define MUSE_INSTANTIATE_RESPONSE_BIG(X, M) MUSE_INSTANTIATE_BIG(X, M)
+#else
+#define MUSE_INSTANTIATE_RESPONSE(X, M) MUSE_INSTANTIATE_STENCIL_MAP(X, M)
+#define MUSE_INSTANTIATE_RESPONSE_BIG(X, M) MUSE_INSTANTIATE_BIG_MAP(X, M)
+#endif
+#define MUSE_PART_0(X) MUSE_INSTANTIATE_RESPONSE(X, UserResponseModel<2>)
+#define MUSE_PART_1(X) MUSE_INSTANTIATE_RESPONSE(X, UserResponseModel<4>)
+#define MUSE_PART_2(X) MUSE_INSTANTIATE_RESPONSE(X, UserResponseModel<kMaxTheta>)
+#define MUSE_PART_3(X) MUSE_INSTANTIATE_RESPONSE_BIG(X, UserResponseModel<kBigTheta>)
+#define MUSE_PART_4(X)
+#define MUSE_PART_5(X)
+#define MUSE_PART_6(X)
+#define MUSE_PART_7(X)
+#elif defined(MUSE_USER_MODEL_HEADER)
 #ifdef MUSE_MODEL_SECOND
-#define MUSE_INSTANTIATE_USER(X, M)                                                                 \
+#define MUSE_INSTANTIATE_USER(X, M)                                                                \
     X template hipError_t launch_place<M>(const LaunchShape&, const BatchArgs&, hipStream_t);       \
     X template hipError_t launch_place_implicit<M>(const LaunchShape&, const BatchArgs&, hipStream_t); \
     X template hipError_t loop_place<M>(const LaunchShape&, const LoopCall&);

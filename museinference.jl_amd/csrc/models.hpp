@@ -120,20 +120,62 @@ struct SmoothLinkModel : SmoothNoiseModel<MAXB_> {
     __device__ static __forceinline__ double a2() { return ((kernarg_f64)__builtin_amdgcn_kernarg_segment_ptr())[offsetof(BatchArgs, link) / 8]; }
     __device__ static __forceinline__ double a3() { return ((kernarg_f64)__builtin_amdgcn_kernarg_segment_ptr())[offsetof(BatchArgs, link) / 8 + 1]; }
 };
+#if defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_RESPONSE)
+// ... and with the response a USER'S header states (include/muse_model.h, MUSE_MODEL_RESPONSE): phi and phi' from
+// muse_model_response(u, p, .), p the same two wavefront-uniform scalars of the launch (BatchArgs::link).  kLink selects every fork
+// SmoothLinkModel takes -- stencil_pairs, stencil_grad_linked, the sampler's second pass, loglike_kernel, the finish kernel --, whose
+// text knows phi through link_value / link_slope / link_rho alone; those three call the header for this type.  The pair is handed
+// over as two values in registers, so that after inlining a header that restates the built-in's expressions IS the built-in's
+// expression tree: the same rounded operations, the same bits.
+template <int MAXB_>
+struct UserResponseModel : SmoothNoiseModel<MAXB_> {
+    static constexpr bool kLink = true;
+    static constexpr bool kResponse = true;
+    __device__ static __forceinline__ double p0() { return ((kernarg_f64)__builtin_amdgcn_kernarg_segment_ptr())[offsetof(BatchArgs, link) / 8]; }
+    __device__ static __forceinline__ double p1() { return ((kernarg_f64)__builtin_amdgcn_kernarg_segment_ptr())[offsetof(BatchArgs, link) / 8 + 1]; }
+    __device__ static __forceinline__ void response(double u, double& phi, double& dphi) {
+        const double p[2] = {p0(), p1()};
+        muse_model_response(u, p, &phi, &dphi);
+    }
+#ifdef MUSE_MODEL_RESPONSE_SECOND   // (the operand of the implicit-differentiation get_H!, Solver::run_implicit_response)
+    __device__ static __forceinline__ double second(double u) {
+        const double p[2] = {p0(), p1()};
+        return muse_model_response_second(u, p);
+    }
+#endif
+};
+#endif
+template <class Model, class = void>
+struct has_response : std::false_type {};
+template <class Model>
+struct has_response<Model, std::void_t<decltype(Model::kResponse)>> : std::true_type {};
+template <class Model>
+constexpr bool response_model() { return has_response<Model>::value; }
 template <class Model>
 constexpr bool link_model() {
     if constexpr (Model::kStencil) return Model::kLink;
     else return false;
 }
 // phi(u) = u + u^2 (a2 + a3 u): three rounded operations beside the load of the coefficients
+// (a user's response: the header's, of whose two results the unused one is dead code behind the inlining)
 template <class Model>
 __device__ __forceinline__ double link_value(double u) {
+    if constexpr (response_model<Model>()) {
+        double phi, dphi;
+        Model::response(u, phi, dphi);
+        return phi;
+    } else
     if constexpr (link_model<Model>()) return fma(u * fma(Model::a3(), u, Model::a2()), u, u);
     else return u;
 }
 // phi'(u) = 1 + u (2 a2 + 3 a3 u) (the two products of the coefficients are scalar work)
 template <class Model>
 __device__ __forceinline__ double link_slope(double u) {
+    if constexpr (response_model<Model>()) {
+        double phi, dphi;
+        Model::response(u, phi, dphi);
+        return dphi;
+    } else
     if constexpr (link_model<Model>()) return fma(u, fma(3.0 * Model::a3(), u, 2.0 * Model::a2()), 1.0);
     else return 1.0;
 }
@@ -215,7 +257,7 @@ struct PairGp { const double* p; bool valid; };
 __host__ __device__ __forceinline__ const double* pair_table(const ThetaSet& t) { return &t.sd[0]; }
 static_assert(offsetof(ThetaSet, iv) == offsetof(ThetaSet, sd) + kMaxTheta * sizeof(double), "sd and iv as one [block][4] table");
 
-#ifdef MUSE_USER_MODEL_HEADER
+#if defined(MUSE_USER_MODEL_HEADER) && !defined(MUSE_MODEL_RESPONSE)   // (a response header: UserResponseModel above, no elementwise model)
 #ifndef MUSE_MODEL_PAIR
 template <int MAXB_>
 struct UserModel {  // include/muse_model.h: the three functions of the user's header behind the elementwise model concept

@@ -170,6 +170,15 @@ static void pair_map_theta(int nt, const int64_t* bnd, const double* theta, MapT
 constexpr bool kPairModel = false;
 #endif
 static int nblocks_of(int ntheta) { return kPairModel ? ntheta / 2 : ntheta; }
+// A library built from a response header (include/muse_model.h, MUSE_MODEL_RESPONSE) holds the stencil model with the header's phi
+// under MUSE_MODEL_USER: such a context is a stencil context wherever the engine asks -- placements, cluster sizes, the direction in
+// LDS, the tiers, set_stencil / set_noise / set_link -- and every launch of it carries a link (muse_ctx_create).
+#if defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_RESPONSE)
+constexpr bool kResponseModel = true;
+#else
+constexpr bool kResponseModel = false;
+#endif
+static bool stencil_ctx(const muse_ctx* c) { return c->model == MUSE_MODEL_SMOOTH || (kResponseModel && c->model == MUSE_MODEL_USER); }
 // exp(theta/2), exp(-theta) and the constant term: step.hpp's fixed sequences (the device-resident loop forms the same bits)
 static void make_thetaset(const muse_ctx* c, const double* theta, ThetaSet& t) {
     MapTheta m;
@@ -204,13 +213,13 @@ static size_t stencil_lds_s_bytes(const muse_ctx* c, int csize) {
     return (size_t)cap * 256 * 16;
 }
 static bool stencil_lds_s(const muse_ctx* c, int csize) {
-    return !c->sw.no_lds_s && c->model == MUSE_MODEL_SMOOTH && csize >= 2 && stencil_lds_s_bytes(c, csize) <= 72 * 1024;
+    return !c->sw.no_lds_s && stencil_ctx(c) && csize >= 2 && stencil_lds_s_bytes(c, csize) <= 72 * 1024;
 }
 static int cluster_size(const muse_ctx* c) {
     if (c->split >= 2) return c->split;
     if (c->sw.cluster_size > 0) return c->sw.cluster_size;  // tuning aid
     // stencil model: clusters of 16 where that lets the search direction live in LDS (N <= ~147 000)
-    if (c->model == MUSE_MODEL_SMOOTH && c->N >= kClusterMinN && c->N < 4194304 && stencil_lds_s(c, 16)) return 16;
+    if (stencil_ctx(c) && c->N >= kClusterMinN && c->N < 4194304 && stencil_lds_s(c, 16)) return 16;
     return c->N >= 4194304 ? 16 : (c->N >= kClusterMinN ? 8 : 1);  // 8: smooth_1e5 2.80 ms (4: 3.22), noise_1e6 1.56 (4: 1.61)
 }
 static bool use_cluster(const muse_ctx* c) { return c->split >= 2 || c->N >= kClusterMinN; }
@@ -223,10 +232,10 @@ static int choose_place(const muse_ctx* c) {
     // the agent-scope release/acquire of the cluster reduction that ends every pass (pass_barrier where a
     // pass has no reduction)
     const bool big = c->ntheta > kMaxTheta;  // the big tier (args.hpp, BigTheta) runs in the streaming placements
-    if (c->split >= 2 && c->split <= 8 && c->model != MUSE_MODEL_SMOOTH && c->placement != 0 && c->N <= kMaxResidentN && !big)
+    if (c->split >= 2 && c->split <= 8 && !stencil_ctx(c) && c->placement != 0 && c->N <= kMaxResidentN && !big)
         return c->split == 2 ? P_CR2 : (c->split == 4 ? P_CR4 : P_CR8);
     if (use_cluster(c)) return P_C256;
-    if (c->model == MUSE_MODEL_SMOOTH || c->placement == 0 || c->N > kMaxResidentN || big) return small ? P_S256 : P_S512;
+    if (stencil_ctx(c) || c->placement == 0 || c->N > kMaxResidentN || big) return small ? P_S256 : P_S512;
     if (small) return P_R256x1;
     if (c->N <= 4096) return P_R512x4;
     return P_R512x10;
@@ -239,7 +248,7 @@ static int choose_place(const muse_ctx* c) {
 static bool tier_big(const muse_ctx* c, int pl, int nmaps) {
     if (c->ntheta > kMaxTheta) return true;
     if (kPairModel) return false;   // (one tier: models.hpp, UserModel of the two-parameter family)
-    return !c->sw.no_big_tier && c->ntheta > 1 && c->model != MUSE_MODEL_SMOOTH && nmaps <= 1 && (pl == P_S256 || pl == P_S512 || pl == P_C256);
+    return !c->sw.no_big_tier && c->ntheta > 1 && !stencil_ctx(c) && nmaps <= 1 && (pl == P_S256 || pl == P_S512 || pl == P_C256);
 }
 static bool ncache_applies(const muse_ctx* c) {
     return !c->sw.no_ncache && choose_place(c) == P_R512x10;
@@ -416,7 +425,7 @@ static int launch_batch(muse_ctx* c, BatchArgs& a, hipEvent_t done = nullptr, bo
         // XCD-local clusters (muse_kernels.hip) for the elementwise models, whose members meet in scalar exchanges only:
         // 22.2 -> 21.3 us at 64 sims split 4, noise_1e6 1.555 -> 1.52 ms.  The stencil model, whose members also stream
         // each other's boundary elements, measured slower with all of a cluster's traffic in one XCD (2.35 -> 2.47 ms).
-        a.xcd_local = (!c->sw.no_xcd_local && ncl % 8 == 0 && c->model != MUSE_MODEL_SMOOTH) ? 1 : 0;
+        a.xcd_local = (!c->sw.no_xcd_local && ncl % 8 == 0 && !stencil_ctx(c)) ? 1 : 0;
     } else {
         if (grid > a.nproblems) grid = a.nproblems;
         if (grid < 1) grid = 1;
@@ -561,6 +570,22 @@ static void set_launch_constants(const muse_ctx* c, BatchArgs& a) {
     }
 }
 
+// the unit noise vectors of a context with a link and no noise map: made once, never written again
+static int ensure_link_unit(muse_ctx* c, const char* who) {
+    if (c->link_unit) return MUSE_OK;
+    std::vector<double> ones((size_t)c->ld, 0.0);   // (the pad element: 0)
+    for (int64_t i = 0; i < c->N; ++i) ones[(size_t)i] = 1.0;
+    double* fresh = nullptr;
+    hipError_t e = hipMalloc(&fresh, (size_t)c->ld * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(fresh, ones.data(), (size_t)c->ld * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        hipFree(fresh);
+        return fail(MUSE_ERR_HIP, std::string(who) + ": the unit noise vector: " + hipGetErrorString(e));
+    }
+    c->link_unit = fresh;
+    return MUSE_OK;
+}
+
 extern "C" {
 
 const char* muse_last_error(void) { return g_err.c_str(); }
@@ -589,7 +614,20 @@ int muse_ctx_create(int model, int64_t N, int ntheta, int device, muse_ctx** out
     if (model == MUSE_MODEL_NOISE && ntheta != 1) return fail(MUSE_ERR_INVALID, "MUSE_MODEL_NOISE has ntheta = 1");
     if (ntheta > N) return fail(MUSE_ERR_INVALID, "ntheta must be <= N");
     if (model == MUSE_MODEL_SMOOTH && N < 5) return fail(MUSE_ERR_INVALID, "MUSE_MODEL_SMOOTH needs N >= 5");
-#ifdef MUSE_USER_MODEL_HEADER
+#if defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_RESPONSE)
+    if (N < 5) return fail(MUSE_ERR_INVALID, "model " MUSE_MODEL_NAME " is a response behind the stencil operator (MUSE_MODEL_RESPONSE): it needs N >= 5");
+    {   // the family's contract (include/muse_model.h): finite at u = 0 -- the pad element's operand
+        const double p00[2] = {0.0, 0.0};
+        double phi = NAN, dphi = NAN, d2 = 0.0;
+        muse_model_response(0.0, p00, &phi, &dphi);
+#ifdef MUSE_MODEL_RESPONSE_SECOND
+        d2 = muse_model_response_second(0.0, p00);
+#endif
+        if (!(isfinite(phi) && isfinite(dphi) && isfinite(d2)))
+            return fail(MUSE_ERR_INVALID, "model " MUSE_MODEL_NAME ": muse_model_response (and muse_model_response_second) must be finite at u = 0 "
+                                          "(include/muse_model.h)");
+    }
+#elif defined(MUSE_USER_MODEL_HEADER)
 #ifdef MUSE_MODEL_N  // a model with per-element tables is built for one N (include/muse_model.h)
     if (N != (int64_t)(MUSE_MODEL_N)) return fail(MUSE_ERR_INVALID, "model " MUSE_MODEL_NAME " was built for another N (MUSE_MODEL_N)");
 #endif
@@ -671,6 +709,14 @@ int muse_ctx_create(int model, int64_t N, int ntheta, int device, muse_ctx** out
     HIPCHK(hipMemsetAsync(c->x_data, 0, (size_t)c->ld * sizeof(double), c->lane->stream));
     HIPCHK(hipMemsetAsync(c->tmp, 0, (size_t)3 * c->ld * sizeof(double), c->lane->stream));
     HIPCHK(hipStreamSynchronize(c->lane->stream));
+    if (kResponseModel) {   // every launch of a response library carries a link: p = (0, 0) and unit noise until they are set
+        const int rc = ensure_link_unit(c, "muse_ctx_create");
+        if (rc) {
+            muse_ctx_destroy(c);
+            return rc;
+        }
+        c->link_on = true;
+    }
     *out = c;
     return MUSE_OK;
 }
@@ -777,7 +823,7 @@ int muse_set_stream(muse_ctx* c, void* s) {
 int muse_set_placement(muse_ctx* c, int placement) {
     if (!c) return fail(MUSE_ERR_INVALID, "ctx is NULL");
     if (placement < -1 || placement > 1) return fail(MUSE_ERR_INVALID, "placement must be -1, 0 or 1");
-    if (placement == 1 && (c->N > kMaxResidentN || c->model == MUSE_MODEL_SMOOTH))
+    if (placement == 1 && (c->N > kMaxResidentN || stencil_ctx(c)))
         return fail(MUSE_ERR_INVALID, "resident placement not available for this problem");
     c->placement = placement;
     return MUSE_OK;
@@ -841,11 +887,11 @@ int muse_synchronize(muse_ctx* c) {
 int muse_set_stencil(muse_ctx* c, const double* w) {
     int rc = check_ctx(c);
     if (rc) return rc;
-#ifdef MUSE_USER_MODEL_HEADER
+#if defined(MUSE_USER_MODEL_HEADER) && !defined(MUSE_MODEL_RESPONSE)
     (void)w;
     return fail(MUSE_ERR_INVALID, "muse_set_stencil: this library was built from a user's model header and holds no stencil model");
 #else
-    if (c->model != MUSE_MODEL_SMOOTH) return fail(MUSE_ERR_INVALID, "muse_set_stencil: the context's model is not MUSE_MODEL_SMOOTH");
+    if (!stencil_ctx(c)) return fail(MUSE_ERR_INVALID, "muse_set_stencil: the context's model is not MUSE_MODEL_SMOOTH");
     if (!w) {   // back to the built-in operator and its kernels
         c->stencil_taps = false;
         c->stencil_w[0] = 0.5;
@@ -863,7 +909,7 @@ int muse_set_stencil(muse_ctx* c, const double* w) {
 int muse_get_stencil(muse_ctx* c, double* w_out, int* runtime_out) {
     int rc = check_ctx(c);
     if (rc) return rc;
-    if (c->model != MUSE_MODEL_SMOOTH) return fail(MUSE_ERR_INVALID, "muse_get_stencil: the context's model is not MUSE_MODEL_SMOOTH");
+    if (!stencil_ctx(c)) return fail(MUSE_ERR_INVALID, "muse_get_stencil: the context's model is not MUSE_MODEL_SMOOTH");
     if (w_out)
         for (int k = 0; k < kStencilWeights; ++k) w_out[k] = c->stencil_w[k];
     if (runtime_out) *runtime_out = c->stencil_taps ? 1 : 0;
@@ -872,11 +918,11 @@ int muse_get_stencil(muse_ctx* c, double* w_out, int* runtime_out) {
 int muse_set_noise(muse_ctx* c, const double* sd, const double* mask, int mem) {
     int rc = check_ctx(c);
     if (rc) return rc;
-#ifdef MUSE_USER_MODEL_HEADER
+#if defined(MUSE_USER_MODEL_HEADER) && !defined(MUSE_MODEL_RESPONSE)
     (void)sd; (void)mask; (void)mem;
     return fail(MUSE_ERR_INVALID, "muse_set_noise: this library was built from a user's model header and holds no stencil model");
 #else
-    if (c->model != MUSE_MODEL_SMOOTH) return fail(MUSE_ERR_INVALID, "muse_set_noise: the context's model is not MUSE_MODEL_SMOOTH");
+    if (!stencil_ctx(c)) return fail(MUSE_ERR_INVALID, "muse_set_noise: the context's model is not MUSE_MODEL_SMOOTH");
     if (mem != MUSE_MEM_HOST && mem != MUSE_MEM_DEVICE) return fail(MUSE_ERR_INVALID, "muse_set_noise: mem must be MUSE_MEM_HOST or MUSE_MEM_DEVICE");
     if (!sd) {   // back to unit noise, every element observed, and the kernels without noise vectors
         rc = muse_synchronize(c);
@@ -939,7 +985,7 @@ int muse_set_noise(muse_ctx* c, const double* sd, const double* mask, int mem) {
 int muse_get_noise(muse_ctx* c, double* sd_out, double* mask_out, int* runtime_out) {
     int rc = check_ctx(c);
     if (rc) return rc;
-    if (c->model != MUSE_MODEL_SMOOTH) return fail(MUSE_ERR_INVALID, "muse_get_noise: the context's model is not MUSE_MODEL_SMOOTH");
+    if (!stencil_ctx(c)) return fail(MUSE_ERR_INVALID, "muse_get_noise: the context's model is not MUSE_MODEL_SMOOTH");
     for (int64_t i = 0; i < c->N; ++i) {
         if (sd_out) sd_out[i] = c->noise_on ? c->noise_sd[(size_t)i] : 1.0;
         if (mask_out) mask_out[i] = c->noise_on ? c->noise_mask[(size_t)i] : 1.0;
@@ -950,30 +996,32 @@ int muse_get_noise(muse_ctx* c, double* sd_out, double* mask_out, int* runtime_o
 int muse_set_link(muse_ctx* c, const double* a) {
     int rc = check_ctx(c);
     if (rc) return rc;
-#ifdef MUSE_USER_MODEL_HEADER
+#if defined(MUSE_USER_MODEL_HEADER) && !defined(MUSE_MODEL_RESPONSE)
     (void)a;
     return fail(MUSE_ERR_INVALID, "muse_set_link: this library was built from a user's model header and holds no stencil model");
 #else
-    if (c->model != MUSE_MODEL_SMOOTH) return fail(MUSE_ERR_INVALID, "muse_set_link: the context's model is not MUSE_MODEL_SMOOTH");
-    if (!a) {   // back to x = A z + noise and the kernels that ran before
-        c->link_on = false;
+    if (!stencil_ctx(c)) return fail(MUSE_ERR_INVALID, "muse_set_link: the context's model is not MUSE_MODEL_SMOOTH");
+    if (!a) {   // back to x = A z + noise and the kernels that ran before (a response library: p = (0, 0), the same kernels)
+        c->link_on = kResponseModel;
         c->link_a[0] = c->link_a[1] = 0.0;
         return MUSE_OK;
     }
     // (every check before anything of the context changes: a refused call leaves it as it was)
-    if (!isfinite(a[0]) || !isfinite(a[1])) return fail(MUSE_ERR_INVALID, "muse_set_link: the coefficients a2 and a3 must be finite");
-    if (!c->link_unit) {   // the unit noise vectors of a context with a link and no noise map: made once, never written again
-        std::vector<double> ones((size_t)c->ld, 0.0);   // (the pad element: 0)
-        for (int64_t i = 0; i < c->N; ++i) ones[(size_t)i] = 1.0;
-        double* fresh = nullptr;
-        hipError_t e = hipMalloc(&fresh, (size_t)c->ld * sizeof(double));
-        if (e == hipSuccess) e = hipMemcpy(fresh, ones.data(), (size_t)c->ld * sizeof(double), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            hipFree(fresh);
-            return fail(MUSE_ERR_HIP, std::string("muse_set_link: the unit noise vector: ") + hipGetErrorString(e));
-        }
-        c->link_unit = fresh;
+    if (!isfinite(a[0]) || !isfinite(a[1])) return fail(MUSE_ERR_INVALID, kResponseModel ? "muse_set_link: the response's numbers p0 and p1 must be finite"
+                                                                                         : "muse_set_link: the coefficients a2 and a3 must be finite");
+#if defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_RESPONSE)
+    {   // the family's contract at the numbers given (include/muse_model.h): finite at u = 0, as muse_ctx_create checked at (0, 0)
+        double phi = NAN, dphi = NAN, d2 = 0.0;
+        muse_model_response(0.0, a, &phi, &dphi);
+#ifdef MUSE_MODEL_RESPONSE_SECOND
+        d2 = muse_model_response_second(0.0, a);
+#endif
+        if (!(isfinite(phi) && isfinite(dphi) && isfinite(d2)))
+            return fail(MUSE_ERR_INVALID, "muse_set_link: model " MUSE_MODEL_NAME " is not finite at u = 0 with these numbers (include/muse_model.h)");
     }
+#endif
+    rc = ensure_link_unit(c, "muse_set_link");
+    if (rc) return rc;
     // (nothing to wait for: a launch in flight carries its own copy of the coefficients)
     c->link_a[0] = a[0];
     c->link_a[1] = a[1];
@@ -984,7 +1032,7 @@ int muse_set_link(muse_ctx* c, const double* a) {
 int muse_get_link(muse_ctx* c, double* a_out, int* runtime_out) {
     int rc = check_ctx(c);
     if (rc) return rc;
-    if (c->model != MUSE_MODEL_SMOOTH) return fail(MUSE_ERR_INVALID, "muse_get_link: the context's model is not MUSE_MODEL_SMOOTH");
+    if (!stencil_ctx(c)) return fail(MUSE_ERR_INVALID, "muse_get_link: the context's model is not MUSE_MODEL_SMOOTH");
     if (a_out) { a_out[0] = c->link_a[0]; a_out[1] = c->link_a[1]; }
     if (runtime_out) *runtime_out = c->link_on ? 1 : 0;
     return MUSE_OK;
@@ -1016,13 +1064,24 @@ int muse_set_constants(muse_ctx* c, int k, const double* values, int64_t count, 
     g_consts_owner = nullptr;   // (the host copies are re-read below)
     own_host_constants(c);
     return MUSE_OK;
+#elif defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_RESPONSE)
+    (void)c; (void)k; (void)values; (void)count; (void)mem;
+    return fail(MUSE_ERR_INVALID, "muse_set_constants: a response behind the stencil operator (MUSE_MODEL_RESPONSE, include/muse_model.h) has no "
+                                  "run-time constants -- the constant slots of a launch carry the noise vectors: what varies per element "
+                                  "travels in x, muse_set_noise's map and mask; the response's two numbers are muse_set_link's");
 #else
     (void)c; (void)k; (void)values; (void)count; (void)mem;
     return fail(MUSE_ERR_INVALID, "this library's model declares no run-time constants (MUSE_MODEL_NCONST, include/muse_model.h)");
 #endif
 }
 int muse_model_has_second(void) {
-#if defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_PAIR)
+#if defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_RESPONSE)
+#ifdef MUSE_MODEL_RESPONSE_SECOND
+    return 1;
+#else
+    return 0;
+#endif
+#elif defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_PAIR)
 #ifdef MUSE_MODEL_PAIR_SECOND
     return 1;
 #else
@@ -1035,7 +1094,22 @@ int muse_model_has_second(void) {
 #endif
 }
 int muse_model_eval(muse_ctx* c, double iv, double sd, double x, double z, double n1, double n2, int64_t i, double* out) {
-#ifdef MUSE_USER_MODEL_HEADER
+#if defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_RESPONSE)
+    // a response behind the stencil operator: (iv, sd) are the response's numbers (p0, p1), x is u; out = {phi, phi', phi'', 0 ...}
+    (void)c; (void)z; (void)n1; (void)n2;   // (no context and no GPU needed)
+    if (!out || i < 0) return fail(MUSE_ERR_INVALID, "bad argument");
+    {
+        const double pp[2] = {iv, sd};
+        for (int k = 0; k < 10; ++k) out[k] = 0.0;   // (ten doubles, as the one-parameter family writes)
+        muse_model_response(x, pp, &out[0], &out[1]);
+#ifdef MUSE_MODEL_RESPONSE_SECOND
+        out[2] = muse_model_response_second(x, pp);
+#else
+        out[2] = NAN;
+#endif
+        return MUSE_OK;
+    }
+#elif defined(MUSE_USER_MODEL_HEADER)
 #ifdef MUSE_MODEL_NCONST
     int rc = check_ctx(c);   // (the model's run-time constants become this context's)
     if (rc) return rc;
@@ -2192,10 +2266,11 @@ static int implicit_impl(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t 
                          const double* theta0, double atol, const CgOptions& cg, double* cols_out, int32_t* cg_iters_out) {
     const int nt = c->ntheta;
     const int64_t ne = e_end - e_begin;
-    if (c->link_on) return fail(MUSE_ERR_INVALID, kLinkImplicitRefusal);
+    if (c->link_on && !kResponseModel) return fail(MUSE_ERR_INVALID, kLinkImplicitRefusal);   // (a response header's phi'': run_implicit_response)
     if (!muse_model_has_second())
         return fail(MUSE_ERR_INVALID, "the implicit-differentiation H needs second derivatives, which this model's header does not "
-                                      "supply (MUSE_MODEL_SECOND or MUSE_MODEL_PAIR_SECOND, include/muse_model.h): use the finite-difference entries");
+                                      "supply (MUSE_MODEL_SECOND, MUSE_MODEL_PAIR_SECOND or MUSE_MODEL_RESPONSE_SECOND, include/muse_model.h): use the "
+                                      "finite-difference entries");
     if (!(cg.reltol >= 0.0) || !(cg.abstol >= 0.0) || !isfinite(cg.reltol) || !isfinite(cg.abstol))
         return fail(MUSE_ERR_INVALID, "cg_reltol and cg_abstol must be finite and >= 0");
     if (cg.flags & ~(MUSE_IMPLICIT_H1_IS_ZERO | MUSE_IMPLICIT_PL_JACOBI)) return fail(MUSE_ERR_INVALID, "unknown bits in flags");
@@ -2209,7 +2284,7 @@ static int implicit_impl(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t 
     const bool jacobi_kernels = pl_jacobi;   // (the two-parameter family's kernels honour the other keywords already)
 #else
     const bool defaults = cg.maxiter >= 1 && cg.reltol == kCgReltolDefault && cg.abstol == 0.0 && cg.flags == 0;
-    if (c->model == MUSE_MODEL_SMOOTH && pl_jacobi)
+    if (stencil_ctx(c) && pl_jacobi)
         return fail(MUSE_ERR_INVALID, "MUSE_IMPLICIT_PL_JACOBI is for the elementwise models, whose Hessian in z is its own diagonal.  The stencil "
                                       "model's is A' Omega A + diag(e^-theta): its conditioning is the operator's (the near-null space of A times "
                                       "a large Omega), which no diagonal touches -- Jacobi-preconditioned CG takes as many iterations there as "
@@ -2225,7 +2300,8 @@ static int implicit_impl(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t 
                                       "MUSE_IMPLICIT_PL_JACOBI (the elementwise built-in models), for headers of the one-parameter family "
                                       "with second derivatives and for headers of the two-parameter family (MUSE_MODEL_SECOND, "
                                       "MUSE_MODEL_PAIR_SECOND, include/muse_model.h)");
-    const bool jacobi_kernels = !defaults;
+    // (a response library: ONE set of implicit kernels, which read every keyword at run time -- solver.hpp, run_implicit_response)
+    const bool jacobi_kernels = !defaults && !kResponseModel;
 #endif
     if (ne == 0) return MUSE_OK;
     if (ne > 0x7fffffff) return fail(MUSE_ERR_INVALID, "batch too large");

@@ -75,7 +75,7 @@ __global__ void __launch_bounds__(256) sample_kernel(BatchArgs a, uint64_t sim, 
         }
     }
 }
-#ifdef MUSE_USER_MODEL_HEADER
+#if defined(MUSE_USER_MODEL_HEADER) && !defined(MUSE_MODEL_RESPONSE)   // (a response header states no draw: the stencil model's is used)
 __global__ void __launch_bounds__(256) sample_user_kernel(BatchArgs a, uint64_t sim, double* __restrict__ x, double* __restrict__ z) {
     const int64_t N = a.N;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
@@ -101,6 +101,7 @@ __global__ void __launch_bounds__(256) normals_kernel(uint64_t seed, uint64_t si
         n2[i] = np.n2;
     }
 }
+#ifndef MUSE_MODEL_RESPONSE   // (a library built from a response header launches smooth_finish_link_kernel only)
 __global__ void __launch_bounds__(256) smooth_finish_kernel(int64_t N, const double* __restrict__ z,
                                                             const double* __restrict__ noise, double* __restrict__ x) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
@@ -134,7 +135,14 @@ __global__ void __launch_bounds__(256) smooth_finish_noise_kernel(BatchArgs a, c
     }
 }
 
-// (... and a response behind the operator, muse_set_link: x = phi(A z) + s n2, the coefficients the launch's, BatchArgs::link)
+#endif
+// (... and a response behind the operator, muse_set_link: x = phi(A z) + s n2, the coefficients the launch's, BatchArgs::link;
+//  in a library built from a response header -- include/muse_model.h, MUSE_MODEL_RESPONSE -- phi is the header's)
+#if defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_RESPONSE)
+typedef UserResponseModel<kMaxTheta> FinishLinkModel;
+#else
+typedef SmoothLinkModel<kMaxTheta> FinishLinkModel;
+#endif
 __global__ void __launch_bounds__(256) smooth_finish_link_kernel(BatchArgs a, const double* __restrict__ z, const double* __restrict__ noise,
                                                                  double* __restrict__ x) {
     const int64_t N = a.N;
@@ -142,7 +150,7 @@ __global__ void __launch_bounds__(256) smooth_finish_link_kernel(BatchArgs a, co
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t im = i == 0 ? N - 1 : i - 1, ip = i == N - 1 ? 0 : i + 1;
         const double si = sn[i];
-        using M = SmoothLinkModel<kMaxTheta>;
+        using M = FinishLinkModel;
         const double xv = fma(si, noise[i], link_value<M>(stencil_apply<M>(z[im], z[i], z[ip])));
         x[i] = si != 0.0 ? xv : 0.0;
     }
@@ -290,6 +298,21 @@ hipError_t launch_solver(const LaunchShape& s, const BatchArgs& a, hipStream_t s
     }
     return s.ntheta == 2 ? launch_place<UserModel<2>>(s, a, st) : s.ntheta <= 4 ? launch_place<UserModel<4>>(s, a, st)
                                                                                 : launch_place<UserModel<kMaxTheta>>(s, a, st);
+#elif defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_RESPONSE)   // ... a response behind the stencil operator: the link model's kernels
+    if (s.model != MUSE_MODEL_USER || !s.link) return hipErrorInvalidValue;
+    if (s.implicit) {   // implicit differentiation: a header that states phi'' (MUSE_MODEL_RESPONSE_SECOND)
+#ifdef MUSE_MODEL_RESPONSE_SECOND
+        if (s.jacobi) return hipErrorInvalidValue;  // (muse_engine.cpp refuses the call before it gets here)
+        if (s.big) return launch_place_implicit<UserResponseModel<kBigTheta>>(s, a, st);
+        return s.ntheta <= 2 ? launch_place_implicit<UserResponseModel<2>>(s, a, st) : s.ntheta <= 4 ? launch_place_implicit<UserResponseModel<4>>(s, a, st)
+                                                                                                  : launch_place_implicit<UserResponseModel<kMaxTheta>>(s, a, st);
+#else
+        return hipErrorInvalidValue;  // (muse_engine.cpp refuses the call before it gets here)
+#endif
+    }
+    if (s.big) return launch_place_big<UserResponseModel<kBigTheta>>(s, a, st);
+    return s.ntheta <= 2 ? launch_place<UserResponseModel<2>>(s, a, st) : s.ntheta <= 4 ? launch_place<UserResponseModel<4>>(s, a, st)
+                                                                                      : launch_place<UserResponseModel<kMaxTheta>>(s, a, st);
 #elif defined(MUSE_USER_MODEL_HEADER)  // a library built from a user's model header holds that model only (user_model.hpp)
     if (s.model != MUSE_MODEL_USER) return hipErrorInvalidValue;
     if (s.big && !s.implicit) return launch_place_big<UserModel<kBigTheta>>(s, a, st);
@@ -366,6 +389,9 @@ static hipError_t loop_dispatch(const LaunchShape& s, const LoopCall& c) {
     return loop_one<MUSE_INSPECT_LOOP>(s, c);
 #elif defined(MUSE_INSPECT)
     return hipErrorNotSupported;
+#elif defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_RESPONSE)
+    (void)c;
+    return s.model != MUSE_MODEL_USER ? hipErrorInvalidValue : hipErrorNotSupported;  // the stencil model streams
 #elif defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_PAIR)
     if (s.model != MUSE_MODEL_USER) return hipErrorInvalidValue;
     return s.ntheta == 2 ? loop_place<UserModel<2>>(s, c) : s.ntheta <= 4 ? loop_place<UserModel<4>>(s, c) : loop_place<UserModel<kMaxTheta>>(s, c);
@@ -478,6 +504,14 @@ hipError_t launch_normals(uint64_t seed, uint64_t sim, int64_t ld, double* slot,
 
 hipError_t launch_sample(int model, bool taps, bool noisy, bool link, const BatchArgs& a, uint64_t sim, double* x, double* z, double* noise, hipStream_t st) {
     const int grid = (int)((a.N + 255) / 256 < 4096 ? (a.N + 255) / 256 : 4096);
+#if defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_RESPONSE)
+    // (the stencil model's draw: z and the normals, then x = phi(A z) + s n2 with the header's phi)
+    (void)taps; (void)noisy;
+    if (model != MUSE_MODEL_USER || !link) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sample_kernel<MUSE_MODEL_SMOOTH>, dim3(grid), dim3(256), 0, st, a, sim, noise, z);
+    hipLaunchKernelGGL(smooth_finish_link_kernel, dim3(grid), dim3(256), 0, st, a, z, noise, x);
+    return hipGetLastError();
+#else
 #ifdef MUSE_USER_MODEL_HEADER
     (void)noise;
     if (model != MUSE_MODEL_USER || taps || noisy || link) return hipErrorInvalidValue;
@@ -494,9 +528,17 @@ hipError_t launch_sample(int model, bool taps, bool noisy, bool link, const Batc
         else hipLaunchKernelGGL(smooth_finish_kernel, dim3(grid), dim3(256), 0, st, a.N, z, noise, x);
     }
     return hipGetLastError();
+#endif
 }
 
 hipError_t launch_loglike(int model, bool taps, bool noise, bool link, const BatchArgs& a, const double* x, const double* z, double* g, double* out, hipStream_t st) {
+#if defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_RESPONSE)
+    (void)taps; (void)noise;
+    if (model != MUSE_MODEL_USER || !link) return hipErrorInvalidValue;
+    if (a.ntheta > kMaxTheta) hipLaunchKernelGGL(loglike_kernel<UserResponseModel<kBigTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
+    else hipLaunchKernelGGL(loglike_kernel<UserResponseModel<kMaxTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
+    return hipGetLastError();
+#else
 #ifdef MUSE_USER_MODEL_HEADER
     if (model != MUSE_MODEL_USER || taps || noise || link) return hipErrorInvalidValue;
 #ifdef MUSE_MODEL_PAIR
@@ -520,6 +562,7 @@ hipError_t launch_loglike(int model, bool taps, bool noise, bool link, const Bat
     else if (a.ntheta > kMaxTheta) hipLaunchKernelGGL(loglike_kernel<SmoothModel<kBigTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
     else hipLaunchKernelGGL(loglike_kernel<SmoothModel<kMaxTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
     return hipGetLastError();
+#endif
 }
 
 }  // namespace muse

@@ -2552,6 +2552,159 @@ struct Solver : PairState<Model::kPair> {
         }
     }
 
+#ifdef MUSE_MODEL_RESPONSE_SECOND
+    // The branch for a response behind the stencil operator (include/muse_model.h, MUSE_MODEL_RESPONSE_SECOND; models.hpp,
+    // UserResponseModel).  With u = A zhat, r = x - phi(u) and u_t = A z_true, for column j:
+    //   Hessian_z logLike w = -[A' (d o (A w)) + e^-theta w],   d_i = omega_i (phi'(u_i)^2 - r_i phi''(u_i)), 0 where masked,
+    //   b = A' (omega o phi'(u) o phi'(u_t) o A (z_true / 2)|_j),   dFdtheta_k = e^-theta_k zhat|_k,   H1 = 0
+    // -- run_implicit's stencil passes and reductions with noise_weigh(omega, .) replaced by the product with a vector.  d and
+    // e = (omega phi'(u)) phi'(u_t) are formed ONCE behind the solve and kept in the fifth and sixth history vectors (the L-BFGS
+    // history is dead once the solve has ended).  The products are ordered so that at phi' = 1, phi'' = 0 every value rounds as
+    // SmoothNoiseModel's: 1 1 - r 0 = 1, omega 1 = omega, (omega 1) 1 = omega.
+    // cg_reltol, cg_abstol and cg_maxiter (0: H = 0) are read at run time, as the JACOBI instantiations read them; the defaults give
+    // run_implicit's tolerance bit for bit.  The Hessian is definite at a MAP but need not be at the crude point a loose atol stops
+    // at (the r phi'' term): every iteration looks at p.Ap, which must be finite and < 0 -- one scalar compare on a reduction's
+    // result, uniform over the cluster -- and otherwise stops the column there, reporting its count as -1 - iterations (muse_hip.h).
+    __device__ __forceinline__ void run_implicit_response(int p, double* wg_scratch, double* lds_x, double* lds_g) {
+        begin<true>(p, wg_scratch, lds_x, lds_g);
+        solve(p);
+        const int64_t ld = a.ld;
+        const int N = (int)a.N, nth = a.ntheta;
+        VH ztrue, v, r, pp, Ap, t1, t2, dd, ee;
+        ztrue.bind(extra, ld);
+        v.bind(wg_scratch + ld, ld);       // g buffer
+        r.bind(wg_scratch + 2 * ld, ld);   // s buffer
+        pp.bind(hist, ld);
+        Ap.bind(hist + ld, ld);
+        t1.bind(hist + 2 * ld, ld);
+        t2.bind(hist + 3 * ld, ld);
+        dd.bind(hist + 4 * ld, ld);
+        ee.bind(hist + 5 * ld, ld);
+        auto Aat = [&](const VH& w, int i) {  // (A w)_i, as run_implicit's
+            const bool valid = i < N;
+            const int ic = valid ? i : 0;
+            const int im = ic == 0 ? N - 1 : ic - 1, ip = ic == N - 1 ? 0 : ic + 1;
+            const double lr = w.get1(im) + w.get1(ip);
+            const double a0 = stencil_fma<Model>(lr, w.get1(ic));
+            return valid ? a0 : 0.0;
+        };
+        const NoiseVec<Model, 0> om;
+        const int split = a.imp_split > 1 ? a.imp_split : 1;
+        const int plist = p + a.p0;
+        const int64_t psim = plist / split;
+        const int j_lo = split > 1 ? plist % split : 0, j_hi = split > 1 ? j_lo + 1 : nth;
+        // ---- d and e, once: zhat's and z_true's neighbours are other threads' (other workgroups') stores
+        pass_barrier();
+        for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
+            const double w = om.get(jj, i);  // unconditional: the pair load is issued at the even element
+            const double xi = x.get(jj, i);
+            const double u = Aat(z, i), ut = Aat(ztrue, i);
+            double phi, fp;
+            Model::response(u, phi, fp);
+            const double fpp = Model::second(u);
+            const double ri = noise_residual<Model>(w, xi - phi);
+            const double curv = fp * fp - ri * fpp;
+            dd.set(jj, i, w != 0.0 ? w * curv : 0.0);
+            ee.set(jj, i, (w * fp) * link_slope<Model>(ut));
+        }, dd, ee);
+        pass_barrier();
+        for (int j = j_lo; j < j_hi; ++j) {
+            // ---- right-hand side b; v = 0, r = p = b ------------------------------------------------
+            double sum[1] = {0.0}, mx[1] = {0.0};
+            for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
+                const double zt = ztrue.get(jj, i);  // unconditional: the pair load is issued at the even element
+                t1.set(jj, i, blk(jj, i) == j ? 0.5 * zt : 0.0);
+            }, t1);
+            pass_barrier();
+            for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) { t2.set(jj, i, ee.get(jj, i) * Aat(t1, i)); }, t2);
+            pass_barrier();
+            for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
+                const double bi = Aat(t2, i);
+                v.set(jj, i, 0.0);
+                r.set(jj, i, bi);
+                pp.set(jj, i, bi);
+                sum[0] = fma(bi, bi, sum[0]);
+            }, v, r, pp);
+            reduce<1, 0>(sum, mx);
+            double rr = sum[0];
+            const double tol_rel = a.cg_reltol * __builtin_sqrt(rr);
+            const double tol = tol_rel > a.cg_abstol ? tol_rel : a.cg_abstol;
+            int it = 0;
+            bool bad = false;
+            while (it < a.cg_maxiter && !(__builtin_sqrt(rr) <= tol)) {
+                // ---- Ap = A_hess p, p.Ap -----------------------------------------------------------
+                double s1[1] = {0.0};
+                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) { t1.set(jj, i, dd.get(jj, i) * Aat(pp, i)); }, t1);
+                pass_barrier();
+                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
+                    const double pi = pp.get(jj, i);
+                    const double api = -(Aat(t1, i) + ivk(jj, i) * pi);
+                    Ap.set(jj, i, api);
+                    s1[0] = fma(pi, api, s1[0]);
+                }, Ap);
+                reduce<1, 0>(s1, mx);
+                if (!(s1[0] < 0.0) || isinf(s1[0])) {   // an indefinite or non-finite Hessian: conjugate gradients does not apply
+                    bad = true;
+                    break;
+                }
+                const double alpha = rr / s1[0];
+                // ---- v += alpha p ; r -= alpha Ap ; r.r ---------------------------------------------
+                double s2[1] = {0.0};
+                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
+                    v.set(jj, i, fma(alpha, pp.get(jj, i), v.get(jj, i)));
+                    const double ri = fma(-alpha, Ap.get(jj, i), r.get(jj, i));
+                    r.set(jj, i, ri);
+                    s2[0] = fma(ri, ri, s2[0]);
+                }, v, r);
+                reduce<1, 0>(s2, mx);
+                const double beta = s2[0] / rr;
+                rr = s2[0];
+                // ---- p = r + beta p (its stores are ordered before the next stencil read by pass_barrier)
+                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
+                    pp.set(jj, i, fma(beta, pp.get(jj, i), r.get(jj, i)));
+                }, pp);
+                pass_barrier();
+                it += 1;
+            }
+            // ---- H[:, j] = -dFdtheta^T v (H1 = 0) ---------------------------------------------------
+            constexpr int NB = kBig ? 8 : MAXB;
+#pragma unroll 1
+            for (int c = 0; c < (kBig ? nth : 1); c += 8) {
+                double acc[NB];
+#pragma unroll
+                for (int b = 0; b < NB; ++b) acc[b] = 0.0;
+                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
+                    const double zi = z.get(jj, i), vi = v.get(jj, i);
+                    const double t = ivk(jj, i) * zi;
+                    if constexpr (MAXB == 1) {
+                        acc[0] = fma(t, vi, acc[0]);
+                    } else {
+                        const int k = blk(jj, i) - c;
+#pragma unroll
+                        for (int b = 0; b < NB; ++b) acc[b] = (k == b) ? fma(t, vi, acc[b]) : acc[b];
+                    }
+                });
+                reduce<NB, 0>(acc, mx);
+                if (tid == 0 && crank == 0) {
+#pragma unroll
+                    for (int b = 0; b < NB; ++b)
+                        if (c + b < nth) a.scores[(psim * nth + c + b) * nth + j] = 0.0 - acc[b];
+                }
+            }
+            if (tid == 0 && crank == 0) {
+                muse_info inf;
+                inf.iterations = bad ? -1 - it : it;
+                inf.f_calls = f_calls;
+                inf.status = status;
+                inf.hist_words = hist_words;
+                inf.f_min = f;
+                inf.gnorm = gmax;
+                a.info[psim * nth + j] = inf;
+            }
+        }
+    }
+#endif
+
 #ifdef MUSE_MODEL_PAIR_SECOND
     // The branch for the two-parameter family (include/muse_model.h, MUSE_MODEL_PAIR_SECOND): column j of H belongs to block
     // j mod K and to parameter kind j / K (a or b).  With the header's q = {ozz, ozx, gza, gzb, sxa, sxb} and the draw's derivatives

@@ -156,8 +156,8 @@ class ShardedMuseProblem:
         return self.local.get_noise()
 
     def set_link(self, link):
-        """The "smooth" model's response coefficients (HipMuseProblem.set_link) on this rank's problem: every rank calls it with the
-        same pair."""
+        """The "smooth" model's response coefficients -- or the two run-time numbers of a ResponseModel's header --
+        (HipMuseProblem.set_link) on this rank's problem: every rank calls it with the same pair."""
         return self.local.set_link(link)
 
     def get_link(self):

@@ -146,7 +146,106 @@ class ElementwiseModel:
         return f"ElementwiseModel({self.name!r}, {self.header!r})"
 
 
-def check_model_consistency(prob, theta, rng=0, n_probe=6, step=1e-5, rtol=2e-5):
+def _defines(source, macro):
+    text = re.sub(r"/\*.*?\*/", "", source, flags=re.S)
+    return re.search(r"^\s*#\s*define\s+" + macro + r"\b", text, flags=re.M) is not None
+
+
+class ResponseModel(ElementwiseModel):
+    """A pointwise response behind the stencil operator, as a header (include/muse_model.h, MUSE_MODEL_RESPONSE): the coupled model
+    x_i = phi((A z)_i; p) + sd_i n_i of model="smooth" -- run-time stencil weights, noise map, mask -- with phi and phi' from the
+    header's muse_model_response(u, p, &phi, &dphi) and, optionally, phi'' (MUSE_MODEL_RESPONSE_SECOND: the implicit-differentiation
+    get_H!, which the built-in link refuses).  p = (p0, p1) are two run-time numbers of the problem:
+
+        model = ResponseModel.packaged("saturating_response")            # phi = u / sqrt(1 + (p0 u)^2)
+        model = ResponseModel.from_expression("softclip", phi="u/sqrt(1 + (p0*u)**2)")      # phi' and phi'' by sympy
+        prob = HipMuseProblem(x, model=model, ntheta=4, stencil=(0.6, 0.2), noise_sd=sd, mask=mask, link=(0.35, 0.0))
+
+    The library holds the model under MUSE_MODEL_USER and compiles the stencil model's kernels only."""
+
+    response = True
+    pair = False
+
+    @classmethod
+    def from_source(cls, name, source, directory=None, constants=None, runtime_constants=None):
+        """Write `source` -- a header that says `#define MUSE_MODEL_RESPONSE 1` before it includes muse_model.h -- as
+        ElementwiseModel.from_source does.  The family has no element index and no constants (the constant slots of a launch carry
+        the noise vectors), and it is the stencil model's, one parameter per block: what muse_model.h would refuse with #error is
+        refused here, before anything is written."""
+        if constants or runtime_constants:
+            raise ValueError("a response header has no per-element constants (include/muse_model.h, MUSE_MODEL_RESPONSE): the constant slots "
+                             "of a launch carry the noise vectors -- what varies per element travels in x, noise_sd and mask")
+        if not _defines(source, "MUSE_MODEL_RESPONSE"):
+            raise ValueError("a response header says `#define MUSE_MODEL_RESPONSE 1` before it includes muse_model.h")
+        for macro, why in (("MUSE_MODEL_PAIR", "the response family is the stencil model's, one parameter per block"),
+                           ("MUSE_MODEL_NCONST", "the constant slots of a launch carry the stencil model's noise vectors")):
+            if _defines(source, macro):
+                raise ValueError(f"MUSE_MODEL_RESPONSE cannot be combined with {macro}: {why}")
+        return super().from_source(name, source, directory=directory)
+
+    @classmethod
+    def from_expression(cls, name, phi, directory=None):
+        """The header from phi alone -- an expression in u, p0, p1 (a string or a sympy expression) of + - * / sqrt and integer or
+        half-integer powers: phi' and phi'' are formed symbolically and printed as IEEE-only C
+        (museinference_jl_amd.symbolic.response_header_from_expression)."""
+        from .symbolic import response_header_from_expression
+        return cls.from_source(name, response_header_from_expression(name, phi), directory=directory)
+
+    @property
+    def has_second(self):
+        """Whether the header states phi'' (MUSE_MODEL_RESPONSE_SECOND), as the model's own library answers it
+        (muse_model_has_second: what HipMuseProblem.has_second_derivatives reports too; builds the library on first use)."""
+        from . import _capi
+        return bool(_capi.load_library(self.library()).muse_model_has_second())
+
+    def eval(self, u, p=(0.0, 0.0)):
+        """(phi, phi', phi'') of the header at u with the numbers p, evaluated on the host by the model's library (muse_model_eval;
+        no context and no GPU); phi'' is NaN for a header without MUSE_MODEL_RESPONSE_SECOND."""
+        import numpy as np
+        from . import _capi
+        lib = _capi.load_library(self.library())
+        out = np.empty(12)
+        _capi.check(lib.muse_model_eval(None, float(p[0]), float(p[1]), float(u), 0.0, 0.0, 0.0, 0, _capi.ptr(out)), lib)
+        return float(out[0]), float(out[1]), float(out[2])
+
+    def __repr__(self):
+        return f"ResponseModel({self.name!r}, {self.header!r})"
+
+
+def _check_response(model, p, us, rtol, h=1e-5):
+    """phi' of a response header against central differences of phi, and phi'' (where stated) against central differences of phi',
+    through the library's host evaluation (ResponseModel.eval).  Returns the worst residual relative to the larger of the value's
+    size and 1; AssertionError beyond rtol."""
+    worst = 0.0
+    for u in us:
+        u = float(u)
+        hu = h * max(1.0, abs(u))
+        f0, fp, fm = model.eval(u, p), model.eval(u + hu, p), model.eval(u - hu, p)
+        pairs = {"phi'": ((fp[0] - fm[0]) / (2 * hu), f0[1])}
+        if f0[2] == f0[2]:
+            pairs["phi''"] = ((fp[1] - fm[1]) / (2 * hu), f0[2])
+        for name, (fd, val) in pairs.items():
+            res = abs(fd - val) / max(1.0, abs(val))
+            assert res <= rtol, (f"model consistency: {name} at u = {u:.9g} is {val:.9g}, the finite difference of the header's own "
+                                 f"function gives {fd:.9g}")
+            worst = max(worst, res)
+    return float(worst)
+
+
+def check_model_consistency(prob, theta=None, rng=0, n_probe=6, step=1e-5, rtol=2e-5, link=None):
+    """The derivatives a hand-written header states against finite differences (what AD guarantees in the reference,
+    src/simple.jl:84-85).  Given a PROBLEM and theta: everything _check_problem_consistency lists, through the problem's own
+    operators -- for a problem of the response family (ResponseModel) also phi' against central differences of phi and phi''
+    against those of phi', at the problem's link numbers ("response").  Given a ResponseModel alone (no problem, no GPU): that
+    last check only, at the numbers `link` (default (0, 0)), through the library's host evaluation."""
+    if isinstance(prob, ResponseModel):
+        # the header alone (no problem, no GPU): phi' and phi'' against central differences of phi and phi' at `link`'s numbers
+        import numpy as np
+        return {"response": _check_response(prob, (0.0, 0.0) if link is None else link, np.linspace(-3.0, 3.0, max(2, n_probe) + 1), rtol)}
+    return _check_problem_consistency(prob, theta, rng, n_probe, step, rtol)
+
+
+def _check_problem_consistency(prob, theta, rng=0, n_probe=6, step=1e-5, rtol=2e-5):
     """What AD guarantees in the reference (src/simple.jl:84-85: the gradients ARE derivatives of the user's logLike) has to be
     checked for a hand-written header: through the problem's own per-simulation operators, at a draw (x, z) ~ P(x, z | theta),
 
@@ -192,7 +291,9 @@ def check_model_consistency(prob, theta, rng=0, n_probe=6, step=1e-5, rtol=2e-5)
         floor = max(floor, 4 * eps * abs(f0) / step / scale)
         res_t = max(res_t, abs((fp - fm) / (2 * step) - s[k]) / scale)
     out = {"grad_z": float(res_z), "grad_theta": float(res_t), "noise_floor": float(floor)}
-    if getattr(prob, "user_model", None) is not None and getattr(prob, "has_second_derivatives", False):
+    if getattr(getattr(prob, "user_model", None), "response", False):
+        out["response"] = _check_response(prob.user_model, prob.get_link()[0], np.linspace(-3.0, 3.0, max(2, n_probe) + 1), rtol)
+    elif getattr(prob, "user_model", None) is not None and getattr(prob, "has_second_derivatives", False):
         if getattr(prob.user_model, "pair", False):
             out["second"] = _check_pair_second(prob.model_eval, prob.model_eval_second, theta, np.asarray(x), z, n_probe, rtol)
         else:

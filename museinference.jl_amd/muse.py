@@ -501,6 +501,24 @@ def _get_H_implicit(result, prob, theta0, rng, nsims, cg_kwargs, skip_errors, H1
         raise NotImplementedError("implicit_diff needs a problem with the implicit_H_batch seam")
     t0 = time.perf_counter()
     Hs, its = prob.implicit_H_batch(rng, 0, remaining, theta0, atol=1e-1, **cg)
+    # A NEGATIVE count, -1 - iterations (include/muse_hip.h): conjugate gradients met a Hessian that is not definite or not finite at
+    # the point the crude fiducial MAP stopped at -- a response behind the stencil operator away from its MAP -- and stopped that
+    # column; the simulation's H is not usable.  An error, or with skip_errors a warning and the simulation dropped (src/muse.jl:393-400).
+    Hs, its = list(Hs), list(its)
+    bad = [s for s in range(len(its)) if np.any(np.asarray(its[s]) < 0)]
+    if bad and not skip_errors:
+        s = bad[0]
+        raise _capi.MuseError(-1, f"get_H! (implicit_diff): conjugate gradients stopped on simulation {s}: the Hessian in z is not negative "
+                                  f"definite (or not finite) where its fiducial MAP stopped (CG counts {np.asarray(its[s]).tolist()}: -1 - iterations) "
+                                  "-- solve the MAP tighter (a smaller grad_z_logLike_atol) or use the finite-difference get_H! (implicit_diff=False)")
+    for s in bad:
+        warnings.warn(f"get_H! (implicit_diff): simulation {s} skipped: conjugate gradients met a Hessian that is not negative definite "
+                      f"(CG counts {np.asarray(its[s]).tolist()})", RuntimeWarning, stacklevel=3)
+    if bad:
+        Hs = [H for s, H in enumerate(Hs) if s not in bad]
+        its = [c for s, c in enumerate(its) if s not in bad]
+    if not Hs and not result.Hs:
+        raise _capi.MuseError(-1, "get_H! (implicit_diff): every simulation was skipped")
     result.Hs = list(result.Hs) + list(Hs)
     result.metadata.setdefault("implicit_diff_cg_hists", []).extend(list(its))
     result.H = np.mean(np.array(result.Hs), axis=0)

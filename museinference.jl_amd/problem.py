@@ -192,7 +192,11 @@ class HipMuseProblem(AbstractMuseProblem):
                                  # that forward attribute access to a HipMuseProblem do not inherit it)
 
     def __init__(self, x, model="funnel", ntheta=1, prior=None, device=0, N=None, constants=None, stencil=None, noise_sd=None, mask=None, link=None):
-        """link: (a2, a3) -- model="smooth" only -- a pointwise response behind the operator, x_i = phi((A z)_i) + sd_i n_i with
+        """model: "funnel", "noise", "smooth", an ElementwiseModel (a user's elementwise header) or a ResponseModel (a user's response
+        behind the stencil operator: "smooth" with the header's phi -- stencil, noise_sd, mask and link apply as for "smooth", link
+        being the header's two run-time numbers (p0, p1); streaming and cluster placements, every finite-difference entry, and the
+        implicit-differentiation get_H! for a header that states phi'').
+        link: (a2, a3) -- model="smooth" only -- a pointwise response behind the operator, x_i = phi((A z)_i) + sd_i n_i with
         phi(u) = u + a2 u^2 + a3 u^3; set_link changes it later.
         noise_sd, mask: -- model="smooth" only -- a noise standard deviation per element (N finite doubles > 0; a scalar is
         broadcast) and which elements were observed (N of True / False, None: all): x_i = (A z)_i + sd_i n_i, masked elements enter
@@ -284,7 +288,10 @@ class HipMuseProblem(AbstractMuseProblem):
         is not monotone makes the posterior in z multi-modal, and which mode a MAP finds is then the caller's business.  Every
         operator, map, finite-difference get_H! and muse() of this problem uses it from the next call on; the implicit-
         differentiation get_H! is refused while a link is set (LINK_IMPLICIT_REFUSAL).  link = None: no link and the kernels that
-        ran before; (0, 0) gives those kernels' results bit for bit."""
+        ran before; (0, 0) gives those kernels' results bit for bit.
+        A problem of a ResponseModel: link = (p0, p1), the two run-time numbers its header's functions receive; None means (0, 0),
+        and get_link always reports run-time True (every launch carries them).  The implicit-differentiation get_H! runs when the
+        header states phi'' (has_second_derivatives)."""
         if link is None:
             self._check(self._lib.muse_set_link(self._ctx, None))
             return
@@ -323,6 +330,9 @@ class HipMuseProblem(AbstractMuseProblem):
         out = np.empty(12)
         self._check(self._lib.muse_model_eval(self._ctx, float(iv), float(sd), float(x), float(z), float(n1), float(n2), int(i),
                                               _capi.ptr(out)))
+        if getattr(self.user_model, "response", False):
+            # a response header (include/muse_model.h, MUSE_MODEL_RESPONSE): `iv` and `sd` were the numbers p0, p1 and `x` was u
+            return dict(zip(("phi", "dphi", "d2phi"), out[:3].tolist()))
         if getattr(self.user_model, "pair", False):
             # a header of the two-parameter family (include/muse_model.h, MUSE_MODEL_PAIR): `iv` and `sd` were the block's parameters a, b
             return dict(zip(("grad", "term", "t0", "c0", "c1", "c2", "c3", "z", "x", "C", "t1"), out.tolist()))
