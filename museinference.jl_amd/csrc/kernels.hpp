@@ -131,7 +131,6 @@ map_score_kernel(const BatchArgs /*read via the kernarg segment*/) {
             wg_barrier<!Model::kStencil>();
             load_problem_theta<!Model::kStencil>(a, args_lds, p, tid);
             if constexpr (IMPLICIT && Model::kPair) sv.template run_implicit_pair<JACOBI>(p, cl_scratch, lds_x, lds_g);
-            else if constexpr (IMPLICIT && response_model<Model>()) sv.run_implicit_response(p, cl_scratch, lds_x, lds_g);
             else if constexpr (IMPLICIT) sv.template run_implicit<JACOBI>(p, cl_scratch, lds_x, lds_g);
             else sv.run(p, cl_scratch, lds_x, lds_g);
         }
@@ -169,7 +168,6 @@ map_score_kernel(const BatchArgs /*read via the kernarg segment*/) {
                 sv.pk[0] = pk0;
                 sv.pk[1] = pk1;
                 if constexpr (IMPLICIT && Model::kPair) sv.template run_implicit_pair<JACOBI>(p, wg_scratch, lds_x, lds_g);
-                else if constexpr (IMPLICIT && response_model<Model>()) sv.run_implicit_response(p, wg_scratch, lds_x, lds_g);
                 else if constexpr (IMPLICIT) sv.template run_implicit<JACOBI>(p, wg_scratch, lds_x, lds_g);
                 else sv.run(p, wg_scratch, lds_x, lds_g);
             }
@@ -965,7 +963,7 @@ hipError_t loop_place(const LaunchShape& s, const LoopCall& c) {
 #if defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_RESPONSE)
 // A response behind the stencil operator (include/muse_model.h, MUSE_MODEL_RESPONSE): the map kernels the link model has -- the
 // streaming and cluster placements in the tiers of 2, 4 and 8 components, the big tier -- and, for a header that states phi''
-// (MUSE_MODEL_RESPONSE_SECOND), the implicit differentiation's (solver.hpp, run_implicit_response).  No loop kernels: the stencil streams.
+// (MUSE_MODEL_RESPONSE_SECOND), the implicit differentiation's (solver.hpp, run_implicit, its response fork).  No loop kernels: the stencil streams.
 #ifdef MUSE_MODEL_RESPONSE_SECOND
 #define MUSE_INSTANTIATE_RESPONSE(X, M) MUSE_INSTANTIATE_STENCIL(X, M)
 #define MUSE_INSTANTIATE_RESPONSE_BIG(X, M) MUSE_INSTANTIATE_BIG(X, M)

@@ -137,7 +137,7 @@ struct UserResponseModel : SmoothNoiseModel<MAXB_> {
         const double p[2] = {p0(), p1()};
         muse_model_response(u, p, &phi, &dphi);
     }
-#ifdef MUSE_MODEL_RESPONSE_SECOND   // (the operand of the implicit-differentiation get_H!, Solver::run_implicit_response)
+#ifdef MUSE_MODEL_RESPONSE_SECOND   // (the operand of the implicit-differentiation get_H!, the response fork of Solver::run_implicit)
     __device__ static __forceinline__ double second(double u) {
         const double p[2] = {p0(), p1()};
         return muse_model_response_second(u, p);

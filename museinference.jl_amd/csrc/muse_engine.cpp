@@ -2266,7 +2266,7 @@ static int implicit_impl(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t 
                          const double* theta0, double atol, const CgOptions& cg, double* cols_out, int32_t* cg_iters_out) {
     const int nt = c->ntheta;
     const int64_t ne = e_end - e_begin;
-    if (c->link_on && !kResponseModel) return fail(MUSE_ERR_INVALID, kLinkImplicitRefusal);   // (a response header's phi'': run_implicit_response)
+    if (c->link_on && !kResponseModel) return fail(MUSE_ERR_INVALID, kLinkImplicitRefusal);   // (a response header's phi'': run_implicit's response fork)
     if (!muse_model_has_second())
         return fail(MUSE_ERR_INVALID, "the implicit-differentiation H needs second derivatives, which this model's header does not "
                                       "supply (MUSE_MODEL_SECOND, MUSE_MODEL_PAIR_SECOND or MUSE_MODEL_RESPONSE_SECOND, include/muse_model.h): use the "
@@ -2300,7 +2300,7 @@ static int implicit_impl(muse_ctx* c, uint64_t seed, int64_t sim_begin, int64_t 
                                       "MUSE_IMPLICIT_PL_JACOBI (the elementwise built-in models), for headers of the one-parameter family "
                                       "with second derivatives and for headers of the two-parameter family (MUSE_MODEL_SECOND, "
                                       "MUSE_MODEL_PAIR_SECOND, include/muse_model.h)");
-    // (a response library: ONE set of implicit kernels, which read every keyword at run time -- solver.hpp, run_implicit_response)
+    // (a response library: ONE set of implicit kernels, which read every keyword at run time -- solver.hpp, run_implicit's response fork)
     const bool jacobi_kernels = !defaults && !kResponseModel;
 #endif
     if (ne == 0) return MUSE_OK;

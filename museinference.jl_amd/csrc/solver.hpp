@@ -2273,6 +2273,64 @@ struct Solver : PairState<Model::kPair> {
     }
 
     // ------------------------------------------------------------------------------------------
+    // get_H! by implicit differentiation, one simulation per workgroup or cluster (src/muse.jl:335-405):
+    //   H = H1 - dFdtheta^T A^{-1} dFdtheta1,  A = Hessian_z logLike at (x, zhat, theta0),
+    // A^{-1} by conjugate gradients (IterativeSolvers.cg: x0 = 0, reltol sqrt(eps), abstol 0, maxiter).  The reference gets the
+    // derivative operands by nested AD; for the compiled-in models they are closed forms (see oracle/muse_oracle.c, mo_implicit_H,
+    // for the list), a user's header states them.  Two branches, picked by the kernel (kernels.hpp): run_implicit (one parameter per
+    // block: the elementwise models, the stencil models, a response behind the stencil) and run_implicit_pair (the two-parameter
+    // family).  Each runs begin and solve, then per column j: the right-hand side, CG (plain_cg, or jacobi_cg in the JACOBI
+    // instantiations), H[:, j] into scores[(sim * ntheta + row) * ntheta + j] and the column's record into info[sim * ntheta + j].
+    // Streaming policy only.  The buffer plan -- the solver's vectors, all dead once the solve has ended:
+    //   extra vector      z_true (keep_value; a user's one-parameter header: dx/dtheta_k)       pair family: xa = dx/da
+    //   g buffer          v, the CG iterate (A^{-1} b at the end)
+    //   s buffer          r, the residual
+    //   history 0, 1      p and A p (jacobi_cg: u and c)
+    //   history 2         t1: stencil scratch; a user's header: ozz = d2 o / dz2                pair family: ozz
+    //   history 3         t2: stencil scratch                                                   pair family: xb = dx/db
+    //   history 4, 5      a response: d and e (run_implicit)
+
+    // The columns of H this workgroup computes.  imp_split == ntheta: ONE column of one simulation's H (few simulations, many theta:
+    // the columns spread over the GPU, each repeating the cheap atol = 1e-1 MAP); imp_split == 1: all columns of its simulation.
+    struct Columns {
+        int64_t psim;
+        int j_lo, j_hi;
+    };
+    __device__ __forceinline__ Columns implicit_columns(int p) const {
+        const int split = a.imp_split > 1 ? a.imp_split : 1;
+        const int plist = p + a.p0;  // position in the list that starts at sim_begin's first column
+        const int j_lo = split > 1 ? plist % split : 0;
+        return {plist / split, j_lo, split > 1 ? j_lo + 1 : a.ntheta};
+    }
+    // (A w)_i, the periodic stencil (models.hpp, stencil_apply); the pad element maps to 0
+    __device__ __forceinline__ double stencil_at(const VH& w, int i) const {
+        const int N = (int)a.N;
+        const bool valid = i < N;
+        const int ic = valid ? i : 0;
+        const int im = ic == 0 ? N - 1 : ic - 1, ip = ic == N - 1 ? 0 : ic + 1;
+        const double lr = w.get1(im) + w.get1(ip);
+        const double a0 = stencil_fma<Model>(lr, w.get1(ic));
+        return valid ? a0 : 0.0;
+    }
+    // The record of column j: the solve's, with CG's count for `iterations` (-1 - count: plain_cg's guard stopped the column, muse_hip.h)
+    __device__ __forceinline__ void write_column_info(int64_t psim, int j, int iterations) {
+        if (tid == 0 && crank == 0) {
+            muse_info inf;
+            inf.iterations = iterations;
+            inf.f_calls = f_calls;
+            inf.status = status;
+            inf.hist_words = hist_words;
+            inf.f_min = f;
+            inf.gnorm = gmax;
+            a.info[psim * a.ntheta + j] = inf;
+        }
+    }
+    // CG's stopping threshold from the run-time keywords: |r|_2 <= max(cg_reltol |b|_2, cg_abstol), rr = |b|^2
+    __device__ __forceinline__ double cg_tolerance(double rr) const {
+        const double tol_rel = a.cg_reltol * __builtin_sqrt(rr);
+        return tol_rel > a.cg_abstol ? tol_rel : a.cg_abstol;
+    }
+
     // The preconditioned CG loop of the JACOBI instantiations (run_implicit<true>, run_implicit_pair<true>), in the order of
     // IterativeSolvers' preconditioned iterable (cg with the keyword Pl), restated from its published algorithm.  From x = 0, r = b,
     // u = 0, rho = 1, an iteration is
@@ -2290,8 +2348,7 @@ struct Solver : PairState<Model::kPair> {
     template <class HA, class HT>
     __device__ __forceinline__ int jacobi_cg(double rr, double rho_next, bool pl_on, VH& v, VH& r, VH& u, VH& c, HA&& hess_at, HT&& hess_times) {
         const int64_t ld = a.ld;
-        const double tol_rel = a.cg_reltol * __builtin_sqrt(rr);
-        const double tol = tol_rel > a.cg_abstol ? tol_rel : a.cg_abstol;
+        const double tol = cg_tolerance(rr);
         double rho = 1.0, mx[1] = {0.0};
         int it = 0;
         while (it < a.cg_maxiter && !(__builtin_sqrt(rr) <= tol)) {
@@ -2326,48 +2383,83 @@ struct Solver : PairState<Model::kPair> {
         return it;
     }
 
+    // The plain CG loop (IterativeSolvers.cg without Pl) from v = 0, r = p = b, rr = |b|^2, down to |r|_2 <= tol, the caller's
+    // threshold, or cg_maxiter iterations.  Three passes and two reductions per iteration; times_p(s1) runs the caller's pass (or
+    // passes) Ap = A p and accumulates p.Ap into s1.  Not jacobi_cg with Pl off: the same mathematics in another order gives other
+    // bits, and the defaults keep the legacy entry's.  GUARD: A is definite at a MAP but need not be at the crude point a loose atol
+    // stops at (a response's r phi'' term), so every iteration looks at p.Ap, which must be finite and < 0 -- one scalar compare on a
+    // reduction's result, uniform over the cluster -- and otherwise stops there and says so.  BARRIER: times_p reads p's neighbours
+    // (the stencil), so the stores of p = r + beta p are ordered before it by a pass_barrier.
+    struct CgEnd {
+        int iterations;
+        bool indefinite;
+    };
+    template <bool GUARD, bool BARRIER, class TP>
+    __device__ __forceinline__ CgEnd plain_cg(double rr, double tol, VH& v, VH& r, VH& pp, VH& Ap, TP&& times_p) {
+        const int64_t ld = a.ld;
+        double mx[1] = {0.0};
+        int it = 0;
+        while (it < a.cg_maxiter && !(__builtin_sqrt(rr) <= tol)) {
+            // ---- Ap = A_hess p, p.Ap -----------------------------------------------------------
+            double s1[1] = {0.0};
+            times_p(s1);
+            reduce<1, 0>(s1, mx);
+            if constexpr (GUARD) {
+                if (!(s1[0] < 0.0) || isinf(s1[0])) return {it, true};   // an indefinite or non-finite Hessian: conjugate gradients does not apply
+            }
+            const double alpha = rr / s1[0];
+            // ---- v += alpha p ; r -= alpha Ap ; r.r ---------------------------------------------
+            double s2[1] = {0.0};
+            for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
+                v.set(jj, i, fma(alpha, pp.get(jj, i), v.get(jj, i)));
+                const double ri = fma(-alpha, Ap.get(jj, i), r.get(jj, i));
+                r.set(jj, i, ri);
+                s2[0] = fma(ri, ri, s2[0]);
+            }, v, r);
+            reduce<1, 0>(s2, mx);
+            const double beta = s2[0] / rr;
+            rr = s2[0];
+            // ---- p = r + beta p -----------------------------------------------------------------
+            for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
+                pp.set(jj, i, fma(beta, pp.get(jj, i), r.get(jj, i)));
+            }, pp);
+            if constexpr (BARRIER) pass_barrier();
+            it += 1;
+        }
+        return {it, false};
+    }
+
     // ------------------------------------------------------------------------------------------
-    // get_H! implicit-differentiation branch for one simulation (src/muse.jl:335-405):
-    //   H = H1 - dFdtheta^T A^{-1} dFdtheta1,  A = Hessian_z logLike at (x, zhat, theta0),
-    // A^{-1} by conjugate gradients (IterativeSolvers.cg: x0 = 0, reltol sqrt(eps), abstol 0, maxiter).
-    // The reference gets the derivative operands by nested AD; for the compiled-in models they are
-    // closed forms (see oracle/muse_oracle.c, mo_implicit_H, for the list).  Streaming policy only:
-    // the CG vectors reuse the solver's g, s and history buffers; z_true sits in the extra vector.
-    // Writes H[p] (row-major ntheta x ntheta) and the CG iteration count of column j to info[p*ntheta+j].
-    // (The two-parameter family has a branch of its own, run_implicit_pair below: the kernel picks it, kernels.hpp.)
+    // The branch of the models with one parameter per block.  H1 and dFdtheta differ by model (the epilogue); A and b:
+    //   elementwise (funnel, noise, a user's header with MUSE_MODEL_SECOND): A is diagonal, one pass per product;
+    //   stencil (smooth; run-time weights; run-time noise Omega): A w = -[A' (Omega o A w) + e^-theta w], b = A' (Omega o A (z_true / 2)|_j);
+    //   a response behind the stencil (include/muse_model.h, MUSE_MODEL_RESPONSE_SECOND; models.hpp, UserResponseModel): with u = A zhat,
+    //     r = x - phi(u), u_t = A z_true the stencil's passes with Omega replaced by d_i = omega_i (phi'(u_i)^2 - r_i phi''(u_i)), 0 where
+    //     masked, in A and by e = (omega phi'(u)) phi'(u_t) in b; dFdtheta_k = e^-theta_k zhat|_k, H1 = 0.  d and e are formed ONCE behind
+    //     the solve.  The products are ordered so that at phi' = 1, phi'' = 0 every value rounds as SmoothNoiseModel's: 1 1 - r 0 = 1,
+    //     omega 1 = omega, (omega 1) 1 = omega.  cg_reltol, cg_abstol and cg_maxiter (0: H = 0) are read at run time, as the JACOBI
+    //     instantiations read them -- the defaults give the other models' tolerance bit for bit -- and plain_cg runs with its guard.
     // JACOBI (elementwise models; kernels of their own, kernels.hpp): every keyword of IterativeSolvers.cg at run time -- cg_reltol,
     // cg_abstol, cg_maxiter = 0, H1-is-zero -- and the loop of its preconditioned iterable, whose Pl is the identity unless
-    // MUSE_IMPLICIT_PL_JACOBI says Diagonal(diag(A)) (jacobi_cg below).
+    // MUSE_IMPLICIT_PL_JACOBI says Diagonal(diag(A)) (jacobi_cg above).
     template <bool JACOBI = false>
     __device__ __forceinline__ void run_implicit(int p, double* wg_scratch, double* lds_x, double* lds_g) {
         static_assert(!JACOBI || !Model::kStencil, "the preconditioned loop is the elementwise models'");
+        constexpr bool kResponse = response_model<Model>();
         begin<true>(p, wg_scratch, lds_x, lds_g);
         solve(p);
         const int64_t ld = a.ld;
-        const int N = (int)a.N, nth = a.ntheta;
-        VH ztrue, v, r, pp, Ap, t1, t2;
+        const int nth = a.ntheta;
+        VH ztrue, v, r, pp, Ap, t1, t2, rd, re;   // (the buffer plan: above)
         ztrue.bind(extra, ld);
-        v.bind(wg_scratch + ld, ld);       // g buffer
-        r.bind(wg_scratch + 2 * ld, ld);   // s buffer
+        v.bind(wg_scratch + ld, ld);
+        r.bind(wg_scratch + 2 * ld, ld);
         pp.bind(hist, ld);
         Ap.bind(hist + ld, ld);
         t1.bind(hist + 2 * ld, ld);
         t2.bind(hist + 3 * ld, ld);
-        auto Aat = [&](const VH& w, int i) {  // (A w)_i, the periodic stencil (models.hpp, stencil_apply); the pad element maps to 0
-            const bool valid = i < N;
-            const int ic = valid ? i : 0;
-            const int im = ic == 0 ? N - 1 : ic - 1, ip = ic == N - 1 ? 0 : ic + 1;
-            const double lr = w.get1(im) + w.get1(ip);
-            const double a0 = stencil_fma<Model>(lr, w.get1(ic));
-            return valid ? a0 : 0.0;
-        };
         const NoiseVec<Model, 0> om;   // (run-time noise: the Hessian is A' Omega A + diag(e^-theta), the right-hand side A' Omega A (z/2)|_k)
-        // imp_split == ntheta: this element is ONE column of one simulation's H (few simulations, many theta: the
-        // columns spread over the GPU, each repeating the cheap atol = 1e-1 MAP); imp_split == 1: all columns
-        const int split = a.imp_split > 1 ? a.imp_split : 1;
-        const int plist = p + a.p0;  // position in the list that starts at sim_begin's first column
-        const int64_t psim = plist / split;
-        const int j_lo = split > 1 ? plist % split : 0, j_hi = split > 1 ? j_lo + 1 : nth;
+        const Columns col = implicit_columns(p);
         const bool h1_zero = JACOBI && (a.imp_flags & MUSE_IMPLICIT_H1_IS_ZERO) != 0;
         const bool pl_on = JACOBI && (a.imp_flags & MUSE_IMPLICIT_PL_JACOBI) != 0;
         // JACOBI: h_i = -diag(A)_i and (A w)_i, in the operands and the expressions of the A p product of the loop below.  Noise and the
@@ -2382,7 +2474,35 @@ struct Solver : PairState<Model::kPair> {
             if constexpr (Model::kId == MUSE_MODEL_NOISE || Model::kId == MUSE_MODEL_USER) return -(hi * wi);
             else return -(wi + ivk(jj, i) * wi);
         };
-        for (int j = j_lo; j < j_hi; ++j) {
+        if constexpr (kResponse) {
+            // ---- d and e, once: zhat's and z_true's neighbours are other threads' (other workgroups') stores
+            rd.bind(hist + 4 * ld, ld);
+            re.bind(hist + 5 * ld, ld);
+            pass_barrier();
+            for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
+                const double w = om.get(jj, i);  // unconditional: the pair load is issued at the even element
+                const double xi = x.get(jj, i);
+                const double u = stencil_at(z, i), ut = stencil_at(ztrue, i);
+                double phi, fp;
+                Model::response(u, phi, fp);
+                const double fpp = Model::second(u);
+                const double ri = noise_residual<Model>(w, xi - phi);
+                const double curv = fp * fp - ri * fpp;
+                rd.set(jj, i, w != 0.0 ? w * curv : 0.0);
+                re.set(jj, i, (w * fp) * link_slope<Model>(ut));
+            }, rd, re);
+            pass_barrier();
+        }
+        // how the stencil passes weigh an element of A w: in the right-hand side and in the Hessian
+        auto weigh_b = [&](int jj, int i, double aw) {
+            if constexpr (kResponse) return re.get(jj, i) * aw;
+            else return noise_weigh<Model>(om.get(jj, i), aw);
+        };
+        auto weigh_A = [&](int jj, int i, double aw) {
+            if constexpr (kResponse) return rd.get(jj, i) * aw;
+            else return noise_weigh<Model>(om.get(jj, i), aw);
+        };
+        for (int j = col.j_lo; j < col.j_hi; ++j) {
             // ---- right-hand side b = dFdtheta1[:, j]; v = 0, r = p = b --------------------------------
             double sum[1] = {0.0}, mx[1] = {0.0};
             double sum2[2] = {0.0, 0.0};   // JACOBI: r.r and c.r, c = Pl \ r
@@ -2392,10 +2512,10 @@ struct Solver : PairState<Model::kPair> {
                     t1.set(jj, i, blk(jj, i) == j ? 0.5 * zt : 0.0);
                 }, t1);
                 pass_barrier();
-                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) { t2.set(jj, i, noise_weigh<Model>(om.get(jj, i), Aat(t1, i))); }, t2);
+                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) { t2.set(jj, i, weigh_b(jj, i, stencil_at(t1, i))); }, t2);
                 pass_barrier();
                 for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
-                    const double bi = Aat(t2, i);
+                    const double bi = stencil_at(t2, i);
                     v.set(jj, i, 0.0);
                     r.set(jj, i, bi);
                     pp.set(jj, i, bi);
@@ -2435,52 +2555,27 @@ struct Solver : PairState<Model::kPair> {
                 reduce<2, 0>(sum2, mx);
                 it = jacobi_cg(sum2[0], sum2[1], pl_on, v, r, pp, Ap, hess_at, hess_times);
             } else {
-            reduce<1, 0>(sum, mx);
-            double rr = sum[0];
-            const double tol = __builtin_sqrt(kEps) * __builtin_sqrt(rr);
-            while (it < a.cg_maxiter && !(__builtin_sqrt(rr) <= tol)) {
-                // ---- Ap = A_hess p, p.Ap -----------------------------------------------------------
-                double s1[1] = {0.0};
-                if constexpr (Model::kStencil) {
-                    for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) { t1.set(jj, i, noise_weigh<Model>(om.get(jj, i), Aat(pp, i))); }, t1);
-                    pass_barrier();
-                    for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
-                        const double pi = pp.get(jj, i);
-                        const double api = -(Aat(t1, i) + ivk(jj, i) * pi);
-                        Ap.set(jj, i, api);
-                        s1[0] = fma(pi, api, s1[0]);
-                    }, Ap);
-                } else {
+                reduce<1, 0>(sum, mx);
+                double tol;
+                if constexpr (kResponse) tol = cg_tolerance(sum[0]);
+                else tol = __builtin_sqrt(kEps) * __builtin_sqrt(sum[0]);
+                const CgEnd end = plain_cg<kResponse, Model::kStencil>(sum[0], tol, v, r, pp, Ap, [&](double (&s1)[1]) {
+                    if constexpr (Model::kStencil) {
+                        for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) { t1.set(jj, i, weigh_A(jj, i, stencil_at(pp, i))); }, t1);
+                        pass_barrier();
+                    }
                     for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
                         const double pi = pp.get(jj, i);
                         double api;
-                        if constexpr (Model::kId == MUSE_MODEL_NOISE) api = -((iv0 + 1.0) * pi);
+                        if constexpr (Model::kStencil) api = -(stencil_at(t1, i) + ivk(jj, i) * pi);
+                        else if constexpr (Model::kId == MUSE_MODEL_NOISE) api = -((iv0 + 1.0) * pi);
                         else if constexpr (Model::kId == MUSE_MODEL_USER) api = -(t1.get(jj, i) * pi);
                         else api = -(pi + ivk(jj, i) * pi);
                         Ap.set(jj, i, api);
                         s1[0] = fma(pi, api, s1[0]);
                     }, Ap);
-                }
-                reduce<1, 0>(s1, mx);
-                const double alpha = rr / s1[0];
-                // ---- v += alpha p ; r -= alpha Ap ; r.r ---------------------------------------------
-                double s2[1] = {0.0};
-                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
-                    v.set(jj, i, fma(alpha, pp.get(jj, i), v.get(jj, i)));
-                    const double ri = fma(-alpha, Ap.get(jj, i), r.get(jj, i));
-                    r.set(jj, i, ri);
-                    s2[0] = fma(ri, ri, s2[0]);
-                }, v, r);
-                reduce<1, 0>(s2, mx);
-                const double beta = s2[0] / rr;
-                rr = s2[0];
-                // ---- p = r + beta p (its stores are ordered before the next stencil read by pass_barrier)
-                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
-                    pp.set(jj, i, fma(beta, pp.get(jj, i), r.get(jj, i)));
-                }, pp);
-                if constexpr (Model::kStencil) pass_barrier();
-                it += 1;
-            }
+                });
+                it = end.indefinite ? -1 - end.iterations : end.iterations;
             }
             // ---- H[:, j] = H1[:, j] - dFdtheta^T v ----------------------------------------------------
             // (big tier: eight rows of the column per pass, as finish() forms its block sums)
@@ -2534,176 +2629,14 @@ struct Solver : PairState<Model::kPair> {
                                 h1 = c + b == j ? 0.5 * (ivj * h1u[0]) : 0.0;
                             }
                             if constexpr (JACOBI) h1 = h1_zero ? 0.0 : h1;   // (src/muse.jl:353; the sums are cheap beside the pass and stay)
-                            a.scores[(psim * nth + c + b) * nth + j] = h1 - acc[b];
+                            a.scores[(col.psim * nth + c + b) * nth + j] = h1 - acc[b];
                         }
                     }
                 }
             }
-            if (tid == 0 && crank == 0) {
-                muse_info inf;
-                inf.iterations = it;
-                inf.f_calls = f_calls;
-                inf.status = status;
-                inf.hist_words = hist_words;
-                inf.f_min = f;
-                inf.gnorm = gmax;
-                a.info[psim * nth + j] = inf;
-            }
+            write_column_info(col.psim, j, it);
         }
     }
-
-#ifdef MUSE_MODEL_RESPONSE_SECOND
-    // The branch for a response behind the stencil operator (include/muse_model.h, MUSE_MODEL_RESPONSE_SECOND; models.hpp,
-    // UserResponseModel).  With u = A zhat, r = x - phi(u) and u_t = A z_true, for column j:
-    //   Hessian_z logLike w = -[A' (d o (A w)) + e^-theta w],   d_i = omega_i (phi'(u_i)^2 - r_i phi''(u_i)), 0 where masked,
-    //   b = A' (omega o phi'(u) o phi'(u_t) o A (z_true / 2)|_j),   dFdtheta_k = e^-theta_k zhat|_k,   H1 = 0
-    // -- run_implicit's stencil passes and reductions with noise_weigh(omega, .) replaced by the product with a vector.  d and
-    // e = (omega phi'(u)) phi'(u_t) are formed ONCE behind the solve and kept in the fifth and sixth history vectors (the L-BFGS
-    // history is dead once the solve has ended).  The products are ordered so that at phi' = 1, phi'' = 0 every value rounds as
-    // SmoothNoiseModel's: 1 1 - r 0 = 1, omega 1 = omega, (omega 1) 1 = omega.
-    // cg_reltol, cg_abstol and cg_maxiter (0: H = 0) are read at run time, as the JACOBI instantiations read them; the defaults give
-    // run_implicit's tolerance bit for bit.  The Hessian is definite at a MAP but need not be at the crude point a loose atol stops
-    // at (the r phi'' term): every iteration looks at p.Ap, which must be finite and < 0 -- one scalar compare on a reduction's
-    // result, uniform over the cluster -- and otherwise stops the column there, reporting its count as -1 - iterations (muse_hip.h).
-    __device__ __forceinline__ void run_implicit_response(int p, double* wg_scratch, double* lds_x, double* lds_g) {
-        begin<true>(p, wg_scratch, lds_x, lds_g);
-        solve(p);
-        const int64_t ld = a.ld;
-        const int N = (int)a.N, nth = a.ntheta;
-        VH ztrue, v, r, pp, Ap, t1, t2, dd, ee;
-        ztrue.bind(extra, ld);
-        v.bind(wg_scratch + ld, ld);       // g buffer
-        r.bind(wg_scratch + 2 * ld, ld);   // s buffer
-        pp.bind(hist, ld);
-        Ap.bind(hist + ld, ld);
-        t1.bind(hist + 2 * ld, ld);
-        t2.bind(hist + 3 * ld, ld);
-        dd.bind(hist + 4 * ld, ld);
-        ee.bind(hist + 5 * ld, ld);
-        auto Aat = [&](const VH& w, int i) {  // (A w)_i, as run_implicit's
-            const bool valid = i < N;
-            const int ic = valid ? i : 0;
-            const int im = ic == 0 ? N - 1 : ic - 1, ip = ic == N - 1 ? 0 : ic + 1;
-            const double lr = w.get1(im) + w.get1(ip);
-            const double a0 = stencil_fma<Model>(lr, w.get1(ic));
-            return valid ? a0 : 0.0;
-        };
-        const NoiseVec<Model, 0> om;
-        const int split = a.imp_split > 1 ? a.imp_split : 1;
-        const int plist = p + a.p0;
-        const int64_t psim = plist / split;
-        const int j_lo = split > 1 ? plist % split : 0, j_hi = split > 1 ? j_lo + 1 : nth;
-        // ---- d and e, once: zhat's and z_true's neighbours are other threads' (other workgroups') stores
-        pass_barrier();
-        for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
-            const double w = om.get(jj, i);  // unconditional: the pair load is issued at the even element
-            const double xi = x.get(jj, i);
-            const double u = Aat(z, i), ut = Aat(ztrue, i);
-            double phi, fp;
-            Model::response(u, phi, fp);
-            const double fpp = Model::second(u);
-            const double ri = noise_residual<Model>(w, xi - phi);
-            const double curv = fp * fp - ri * fpp;
-            dd.set(jj, i, w != 0.0 ? w * curv : 0.0);
-            ee.set(jj, i, (w * fp) * link_slope<Model>(ut));
-        }, dd, ee);
-        pass_barrier();
-        for (int j = j_lo; j < j_hi; ++j) {
-            // ---- right-hand side b; v = 0, r = p = b ------------------------------------------------
-            double sum[1] = {0.0}, mx[1] = {0.0};
-            for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
-                const double zt = ztrue.get(jj, i);  // unconditional: the pair load is issued at the even element
-                t1.set(jj, i, blk(jj, i) == j ? 0.5 * zt : 0.0);
-            }, t1);
-            pass_barrier();
-            for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) { t2.set(jj, i, ee.get(jj, i) * Aat(t1, i)); }, t2);
-            pass_barrier();
-            for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
-                const double bi = Aat(t2, i);
-                v.set(jj, i, 0.0);
-                r.set(jj, i, bi);
-                pp.set(jj, i, bi);
-                sum[0] = fma(bi, bi, sum[0]);
-            }, v, r, pp);
-            reduce<1, 0>(sum, mx);
-            double rr = sum[0];
-            const double tol_rel = a.cg_reltol * __builtin_sqrt(rr);
-            const double tol = tol_rel > a.cg_abstol ? tol_rel : a.cg_abstol;
-            int it = 0;
-            bool bad = false;
-            while (it < a.cg_maxiter && !(__builtin_sqrt(rr) <= tol)) {
-                // ---- Ap = A_hess p, p.Ap -----------------------------------------------------------
-                double s1[1] = {0.0};
-                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) { t1.set(jj, i, dd.get(jj, i) * Aat(pp, i)); }, t1);
-                pass_barrier();
-                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
-                    const double pi = pp.get(jj, i);
-                    const double api = -(Aat(t1, i) + ivk(jj, i) * pi);
-                    Ap.set(jj, i, api);
-                    s1[0] = fma(pi, api, s1[0]);
-                }, Ap);
-                reduce<1, 0>(s1, mx);
-                if (!(s1[0] < 0.0) || isinf(s1[0])) {   // an indefinite or non-finite Hessian: conjugate gradients does not apply
-                    bad = true;
-                    break;
-                }
-                const double alpha = rr / s1[0];
-                // ---- v += alpha p ; r -= alpha Ap ; r.r ---------------------------------------------
-                double s2[1] = {0.0};
-                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
-                    v.set(jj, i, fma(alpha, pp.get(jj, i), v.get(jj, i)));
-                    const double ri = fma(-alpha, Ap.get(jj, i), r.get(jj, i));
-                    r.set(jj, i, ri);
-                    s2[0] = fma(ri, ri, s2[0]);
-                }, v, r);
-                reduce<1, 0>(s2, mx);
-                const double beta = s2[0] / rr;
-                rr = s2[0];
-                // ---- p = r + beta p (its stores are ordered before the next stencil read by pass_barrier)
-                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
-                    pp.set(jj, i, fma(beta, pp.get(jj, i), r.get(jj, i)));
-                }, pp);
-                pass_barrier();
-                it += 1;
-            }
-            // ---- H[:, j] = -dFdtheta^T v (H1 = 0) ---------------------------------------------------
-            constexpr int NB = kBig ? 8 : MAXB;
-#pragma unroll 1
-            for (int c = 0; c < (kBig ? nth : 1); c += 8) {
-                double acc[NB];
-#pragma unroll
-                for (int b = 0; b < NB; ++b) acc[b] = 0.0;
-                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
-                    const double zi = z.get(jj, i), vi = v.get(jj, i);
-                    const double t = ivk(jj, i) * zi;
-                    if constexpr (MAXB == 1) {
-                        acc[0] = fma(t, vi, acc[0]);
-                    } else {
-                        const int k = blk(jj, i) - c;
-#pragma unroll
-                        for (int b = 0; b < NB; ++b) acc[b] = (k == b) ? fma(t, vi, acc[b]) : acc[b];
-                    }
-                });
-                reduce<NB, 0>(acc, mx);
-                if (tid == 0 && crank == 0) {
-#pragma unroll
-                    for (int b = 0; b < NB; ++b)
-                        if (c + b < nth) a.scores[(psim * nth + c + b) * nth + j] = 0.0 - acc[b];
-                }
-            }
-            if (tid == 0 && crank == 0) {
-                muse_info inf;
-                inf.iterations = bad ? -1 - it : it;
-                inf.f_calls = f_calls;
-                inf.status = status;
-                inf.hist_words = hist_words;
-                inf.f_min = f;
-                inf.gnorm = gmax;
-                a.info[psim * nth + j] = inf;
-            }
-        }
-    }
-#endif
 
 #ifdef MUSE_MODEL_PAIR_SECOND
     // The branch for the two-parameter family (include/muse_model.h, MUSE_MODEL_PAIR_SECOND): column j of H belongs to block
@@ -2712,21 +2645,20 @@ struct Solver : PairState<Model::kPair> {
     //   A w = -ozz w,   b = dFdtheta1[:, j] = -ozx x_kind (the column's block),   rows k and K + k of dFdtheta^T v = -sum gza v, -sum gzb v,
     //   H1[k][j] = sum sxa x_kind,  H1[K + k][j] = sum sxb x_kind over the column's block (skipped when the caller says H1 is zero).
     // The extra vector holds ONE value per element, so nothing kept of the draw is used: behind the solve a pass draws the normals again
-    // (the same generator sequence, so the same bits) and stores xa in the extra vector and xb in the fourth history vector, which
-    // the elementwise CG does not use -- the L-BFGS history is dead once the solve has ended -- together with ozz for the CG passes.
+    // (the same generator sequence, so the same bits) and stores xa, xb and ozz where the buffer plan above says.
     // CG stops at |r| <= max(cg_reltol |b|, cg_abstol) or after cg_maxiter iterations (0: H = H1).
     // JACOBI (kernels of their own, kernels.hpp): the preconditioned loop, Pl = Diagonal(-ozz) (jacobi_cg above).  Every history
-    // vector is taken (p / u, A p, ozz, xb), so c = r / d is formed where it is used; the diagonal is t1, which the loop reads anyway.
+    // vector is taken, so c = r / d is formed where it is used; the diagonal is t1, which the loop reads anyway.
     template <bool JACOBI = false>
     __device__ __forceinline__ void run_implicit_pair(int p, double* wg_scratch, double* lds_x, double* lds_g) {
         begin<true>(p, wg_scratch, lds_x, lds_g);
         solve(p);
         const int64_t ld = a.ld;
         const int N = (int)a.N, nth = a.ntheta, K = nth >> 1;
-        VH xa, xb, xq, v, r, pp, Ap, t1;
+        VH xa, xb, xq, v, r, pp, Ap, t1;   // (the buffer plan: above)
         xa.bind(extra, ld);
-        v.bind(wg_scratch + ld, ld);       // g buffer
-        r.bind(wg_scratch + 2 * ld, ld);   // s buffer
+        v.bind(wg_scratch + ld, ld);
+        r.bind(wg_scratch + 2 * ld, ld);
         pp.bind(hist, ld);
         Ap.bind(hist + ld, ld);
         t1.bind(hist + 2 * ld, ld);
@@ -2744,13 +2676,10 @@ struct Solver : PairState<Model::kPair> {
                 t1.set(jj, i, q[0]);
             }, xa, xb, t1);
         }
-        const int split = a.imp_split > 1 ? a.imp_split : 1;
-        const int plist = p + a.p0;  // position in the list that starts at sim_begin's first column
-        const int64_t psim = plist / split;
-        const int j_lo = split > 1 ? plist % split : 0, j_hi = split > 1 ? j_lo + 1 : nth;
-        const bool h1_zero = (a.imp_flags & 1) != 0;
+        const Columns col = implicit_columns(p);
+        const bool h1_zero = (a.imp_flags & MUSE_IMPLICIT_H1_IS_ZERO) != 0;
         const bool pl_on = JACOBI && (a.imp_flags & MUSE_IMPLICIT_PL_JACOBI) != 0;
-        for (int j = j_lo; j < j_hi; ++j) {
+        for (int j = col.j_lo; j < col.j_hi; ++j) {
             const int kb = j < K ? j : j - K;   // the column's block; its parameter kind selects the draw's derivative
             xq.bind(j < K ? extra : hist + 3 * ld, ld);
             // ---- right-hand side b = dFdtheta1[:, j]; v = 0, r = p = b --------------------------------
@@ -2779,38 +2708,15 @@ struct Solver : PairState<Model::kPair> {
                 it = jacobi_cg(sum2[0], sum2[1], pl_on, v, r, pp, Ap, [&](int jj, int i) { return t1.get(jj, i); },
                                [&](int, int, double wi, double hi) { return -(hi * wi); });
             } else {
-            reduce<1, 0>(sum, mx);
-            double rr = sum[0];
-            const double tol_rel = a.cg_reltol * __builtin_sqrt(rr);
-            const double tol = tol_rel > a.cg_abstol ? tol_rel : a.cg_abstol;
-            while (it < a.cg_maxiter && !(__builtin_sqrt(rr) <= tol)) {
-                // ---- Ap = A_hess p, p.Ap -----------------------------------------------------------
-                double s1[1] = {0.0};
-                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
-                    const double pi = pp.get(jj, i);
-                    const double api = -(t1.get(jj, i) * pi);
-                    Ap.set(jj, i, api);
-                    s1[0] = fma(pi, api, s1[0]);
-                }, Ap);
-                reduce<1, 0>(s1, mx);
-                const double alpha = rr / s1[0];
-                // ---- v += alpha p ; r -= alpha Ap ; r.r ---------------------------------------------
-                double s2[1] = {0.0};
-                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
-                    v.set(jj, i, fma(alpha, pp.get(jj, i), v.get(jj, i)));
-                    const double ri = fma(-alpha, Ap.get(jj, i), r.get(jj, i));
-                    r.set(jj, i, ri);
-                    s2[0] = fma(ri, ri, s2[0]);
-                }, v, r);
-                reduce<1, 0>(s2, mx);
-                const double beta = s2[0] / rr;
-                rr = s2[0];
-                // ---- p = r + beta p -----------------------------------------------------------------
-                for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
-                    pp.set(jj, i, fma(beta, pp.get(jj, i), r.get(jj, i)));
-                }, pp);
-                it += 1;
-            }
+                reduce<1, 0>(sum, mx);
+                it = plain_cg<false, false>(sum[0], cg_tolerance(sum[0]), v, r, pp, Ap, [&](double (&s1)[1]) {
+                    for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
+                        const double pi = pp.get(jj, i);
+                        const double api = -(t1.get(jj, i) * pi);
+                        Ap.set(jj, i, api);
+                        s1[0] = fma(pi, api, s1[0]);
+                    }, Ap);
+                }).iterations;
             }
             // ---- H[:, j] = H1[:, j] - dFdtheta^T v: rows k and K + k of every block, the two H1 sums of the column's block ----
             double acc[MAXB], h1s[2] = {0.0, 0.0};
@@ -2836,18 +2742,11 @@ struct Solver : PairState<Model::kPair> {
                 for (int b = 0; b < MAXB; ++b) {
                     if (b < nth) {
                         const double h1 = b == kb ? h1s[0] : (b == kb + K ? h1s[1] : 0.0);
-                        a.scores[(psim * nth + b) * nth + j] = h1 - acc[b];
+                        a.scores[(col.psim * nth + b) * nth + j] = h1 - acc[b];
                     }
                 }
-                muse_info inf;
-                inf.iterations = it;
-                inf.f_calls = f_calls;
-                inf.status = status;
-                inf.hist_words = hist_words;
-                inf.f_min = f;
-                inf.gnorm = gmax;
-                a.info[psim * nth + j] = inf;
             }
+            write_column_info(col.psim, j, it);
         }
     }
 #endif

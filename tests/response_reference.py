@@ -282,7 +282,7 @@ def numpy_objective(x, z, theta, w, omega, fns, total=lambda v: float(np.sum(v))
 
 
 def numpy_cg(x, zh, zt, theta, w, omega, fns, j, reltol=1.4901161193847656e-08, abstol=0.0, maxiter=200, d=None):
-    """The kernel's CG for column j in fp64 (solver.hpp, run_implicit_response): returns (v with -Hessian v = b, count); the count
+    """The kernel's CG for column j in fp64 (solver.hpp, run_implicit with plain_cg and its guard): returns (v with -Hessian v = b, count); the count
     is -1 - iterations when p.Ap is not finite and negative (an indefinite Hessian).  `d` overrides the curvature vector."""
     N = x.size
     th = np.asarray(theta, np.float64)
