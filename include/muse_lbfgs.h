@@ -1,0 +1,65 @@
+/* muse_lbfgs.h -- libmuse_lbfgs.so: lock-step L-BFGS / HagerZhang for a batch of problems whose objective is the CALLER's
+ * (reverse communication: the objective of every problem is evaluated by the caller, once per round for the whole batch; everything
+ * between two evaluations -- the directional derivative, the line search's state machine, acceptance, the convergence tests, the
+ * history update, the two-loop recursion, the next trial point -- runs for all problems in one kernel launch, one workgroup per
+ * problem).  The algorithm is optim.lbfgs of the Python package decision for decision (Optim.jl's LBFGS(m = 10) with
+ * LineSearches' InitialStatic(1) and HagerZhang defaults); only the order of summation inside a dot product differs.
+ *
+ * A library of its own, apart from libmuse_hip.so (include/muse_hip.h), with no context and no state: all state lives in a workspace
+ * the caller allocates on the device.  No entry point allocates, synchronises or reads the device; every launch goes to `stream`
+ * (a hipStream_t; NULL: the default stream), so the calls order with the caller's own work on that stream.  Because nothing is read
+ * back, the batch's shape (nprob, n, m) is an argument of every call; it must be the same from begin to result.
+ *
+ *     bytes = muse_lbfgs_workspace_bytes(nprob, n, m);                  ws: that many bytes of device memory, 256-byte aligned
+ *     muse_lbfgs_begin(ws, nprob, n, m, z0, g_tol, maxiter, z_eval, stream);
+ *     do {
+ *         f[b], g[b][:] = objective and gradient of problem b at z_eval[b][:]          (the caller's, for every b)
+ *         muse_lbfgs_advance(ws, nprob, n, m, f, g, z_eval, active, stream);
+ *         synchronise the stream
+ *     } while (*active > 0);
+ *     muse_lbfgs_result(ws, nprob, n, m, z_out, info_out, stream);
+ *
+ * z0, z_eval, g, z_out: [nprob][n] doubles in device memory, dense rows (stride n; any 8-byte alignment).  f: [nprob] doubles in
+ * device memory.  A problem's result depends on its own inputs only: not on the batch, nor on its place in it.  A finished
+ * problem's z_eval row stays at its final point (the objective keeps seeing finite input), its record no longer changes and the
+ * values passed for it are ignored.
+ *
+ * Every function returns 0, or a negative number: MUSE_LBFGS_BAD_ARGUMENT, or -(100 + the hipError_t of a failed launch).
+ */
+#ifndef MUSE_LBFGS_H
+#define MUSE_LBFGS_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define MUSE_LBFGS_M 10                /* the history length: the only value of m the library accepts */
+#define MUSE_LBFGS_BAD_ARGUMENT (-1)
+
+/* the workspace's size in bytes (negative: a bad argument) */
+int64_t muse_lbfgs_workspace_bytes(int64_t nprob, int64_t n, int m);
+
+/* start nprob problems at z0 with gradient tolerance g_tol and at most maxiter iterations; writes the first evaluation point (z0
+ * itself) into z_eval */
+int muse_lbfgs_begin(void* ws, int64_t nprob, int64_t n, int m, const double* z0, double g_tol, int maxiter, double* z_eval, void* stream);
+
+/* one round: consumes f and g at z_eval, writes the next z_eval row of every active problem, and stores the number of problems
+ * still active to *active_out -- one int, in pinned host memory (or any memory the device can write); valid once the stream has
+ * reached this point */
+int muse_lbfgs_advance(void* ws, int64_t nprob, int64_t n, int m, const double* f, const double* g, double* z_eval, int* active_out,
+                       void* stream);
+
+/* the minimisers z_out [nprob][n] and one record per problem in info_out (device memory), in the layout of muse_hip.h's solver info:
+ * int32 iterations, f_calls, status, hist_words (0); double f_min, gnorm.  status: 0 g_converged, 1 x_converged, 2 f_converged,
+ * 3 maxiter, 4 linesearch_failed, 5 nonfinite */
+int muse_lbfgs_result(void* ws, int64_t nprob, int64_t n, int m, double* z_out, void* info_out, void* stream);
+
+/* the advance kernel's workgroup size for rows of length n (a function of n alone) */
+int muse_lbfgs_workgroup_size(int64_t n);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

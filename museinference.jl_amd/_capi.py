@@ -148,6 +148,40 @@ def load_library(path=None):
     return lib
 
 
+# libmuse_lbfgs.so (include/muse_lbfgs.h): a library and a table of its own -- SIGNATURES above is libmuse_hip.so's, symbol for symbol
+LBFGS_M = 10
+LBFGS_SIGNATURES = {
+    "muse_lbfgs_workspace_bytes": (_i64, [_i64, _i64, _i]),
+    "muse_lbfgs_begin": (_i, [_vp, _i64, _i64, _i, _vp, _d, _i, _vp, _vp]),
+    "muse_lbfgs_advance": (_i, [_vp, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
+    "muse_lbfgs_result": (_i, [_vp, _i64, _i64, _i, _vp, _vp, _vp]),
+    "muse_lbfgs_workgroup_size": (_i, [_i64]),
+}
+_lbfgs_lib = None
+
+
+def load_lbfgs_library():
+    """dlopen libmuse_lbfgs.so (built in-tree by build.build_lbfgs_library) and declare every signature."""
+    global _lbfgs_lib
+    if _lbfgs_lib is None:
+        path = _build.LBFGS_LIB_PATH
+        if not os.path.exists(path):
+            raise MuseError(-2, f"{path} is missing: run museinference.jl_amd.build.build_lbfgs_library() (there is no CPU fallback)")
+        lib = C.CDLL(path)
+        for name, (res, args) in LBFGS_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _lbfgs_lib = lib
+    return _lbfgs_lib
+
+
+def check_lbfgs(rc):
+    if rc < 0:
+        raise MuseError(rc, "libmuse_lbfgs: a bad argument" if rc == -1 else f"libmuse_lbfgs: launch failed with hipError {-rc - 100}")
+    return rc
+
+
 def check(rc, lib=None):
     """Raise MuseError for a negative status, with the message of the library the call went to."""
     if rc != 0:

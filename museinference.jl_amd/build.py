@@ -179,6 +179,51 @@ def build_packaged_models(force=False):
     return out
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# libmuse_lbfgs.so (include/muse_lbfgs.h): the batched reverse-communication L-BFGS behind simple.BatchedTorchMuseProblem.  A library
+# of its own with sources of its own (lbfgs/, NOT csrc/: the product library, the model libraries and bench.csrc_fingerprint() are
+# defined by what lies under csrc/); it includes csrc/reduce.hpp unchanged.
+LBFGS_DIR = os.path.join(_HERE, "lbfgs")
+LBFGS_LIB_PATH = os.path.join(_HERE, "libmuse_lbfgs.so")
+_LBFGS_API = os.path.join(INCLUDE_DIR, "muse_lbfgs.h")
+_LBFGS_SOURCE = os.path.join(LBFGS_DIR, "lbfgs_kernels.hip")
+_LBFGS_DEPS = [_LBFGS_SOURCE, os.path.join(LBFGS_DIR, "lbfgs_control.hpp"), os.path.join(LBFGS_DIR, "lbfgs_advance.hpp"), _LBFGS_API,
+               os.path.join(CSRC, "reduce.hpp"), os.path.join(CSRC, "args.hpp")]
+
+
+def lbfgs_declared_symbols():
+    """The entry points include/muse_lbfgs.h declares (comments stripped): libmuse_lbfgs.so's export list."""
+    import re
+    text = re.sub(r"/\*.*?\*/", "", open(_LBFGS_API).read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(muse_lbfgs_[a-z_A-Z0-9]+)\s*\(", text)))
+
+
+def build_lbfgs_library(force=False, verbose=False):
+    """Compile (if missing or stale) libmuse_lbfgs.so next to libmuse_hip.so; returns its path."""
+    if not force and not _stale(LBFGS_LIB_PATH, _LBFGS_DEPS):
+        return LBFGS_LIB_PATH
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        raise RuntimeError("hipcc not found: cannot build libmuse_lbfgs.so")
+    with _BuildLock(LBFGS_LIB_PATH):
+        if not force and not _stale(LBFGS_LIB_PATH, _LBFGS_DEPS):
+            return LBFGS_LIB_PATH
+        obj_dir = os.path.join(_HERE, "build_libmuse_lbfgs")
+        os.makedirs(obj_dir, exist_ok=True)
+        obj = os.path.join(obj_dir, "lbfgs_kernels.o")
+        vmap = os.path.join(obj_dir, "exports.map")
+        with open(vmap, "w") as f:
+            f.write("{\n  global:\n" + "".join(f"    {n};\n" for n in lbfgs_declared_symbols()) + "  local: *;\n};\n")
+        tmp = LBFGS_LIB_PATH + ".tmp"
+        for cmd in ([hipcc] + COMMON_FLAGS + _DEVICE_FLAGS + ["-c", _LBFGS_SOURCE, "-o", obj],
+                    [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", obj, "-o", tmp, f"-Wl,--version-script={vmap}"]):
+            if verbose:
+                print(" ".join(cmd))
+            subprocess.check_call(cmd, cwd=LBFGS_DIR)
+        os.replace(tmp, LBFGS_LIB_PATH)
+    return LBFGS_LIB_PATH
+
+
 if __name__ == "__main__":
     import sys
     if "--stamps" in sys.argv:  # the -DMUSE_STAMPS diagnostic build read by tools/stamps.py

@@ -189,6 +189,245 @@ class TorchMuseProblem(AbstractMuseProblem):
         return H.detach().cpu().numpy().astype(np.float64).reshape(n, n)
 
 
+class LbfgsBatch:
+    """libmuse_lbfgs.so (include/muse_lbfgs.h) for one batch shape [nprob, n] on a GPU: the workspace, the evaluation points and the
+    word the kernel reports into are allocated once, as torch tensors; every launch goes to torch's current stream.
+
+        batch.begin(z0, g_tol);  repeat: f, g at batch.z_eval -> active = batch.advance(f, g)  until active == 0;  batch.result()
+    """
+
+    def __init__(self, device, nprob, n):
+        import torch
+        from . import _capi
+        self._torch, self._capi, self._lib = torch, _capi, _capi.load_lbfgs_library()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _capi.MuseError(-3, "no HIP device available (libmuse_lbfgs has no CPU fallback)")
+        self.nprob, self.n, self.m = int(nprob), int(n), _capi.LBFGS_M
+        nbytes = _capi.check_lbfgs(self._lib.muse_lbfgs_workspace_bytes(self.nprob, self.n, self.m))
+        self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.z_eval = torch.empty((self.nprob, self.n), dtype=torch.float64, device=self.device)
+        self._active = torch.zeros(1, dtype=torch.int32).pin_memory()
+        self._info = torch.empty(self.nprob * _capi.INFO_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+        self.rounds = self.syncs = 0
+        self.timing, self.advance_ms = False, 0.0      # timing: device time of the advance launches, summed (tools/closures_bench.py)
+
+    def _stream(self):
+        return self._torch.cuda.current_stream(self.device).cuda_stream
+
+    def _rows(self, t, shape):
+        torch = self._torch
+        if not (torch.is_tensor(t) and t.device == self.z_eval.device and t.dtype == torch.float64 and tuple(t.shape) == shape):
+            raise ValueError(f"expected a float64 tensor of shape {shape} on {self.z_eval.device}")
+        return t.contiguous()
+
+    def begin(self, z0, g_tol, maxiter=1000):
+        z0 = self._rows(z0, (self.nprob, self.n))
+        with self._torch.cuda.device(self.device):
+            self._capi.check_lbfgs(self._lib.muse_lbfgs_begin(self._ws.data_ptr(), self.nprob, self.n, self.m, z0.data_ptr(), float(g_tol),
+                                                              int(maxiter), self.z_eval.data_ptr(), self._stream()))
+        self.rounds = self.syncs = 0
+
+    def advance(self, f, g):
+        """One round: f [nprob], g [nprob, n] at z_eval.  Returns the number of problems still active (the round's ONE synchronisation)."""
+        f, g = self._rows(f, (self.nprob,)), self._rows(g, (self.nprob, self.n))
+        stream = self._torch.cuda.current_stream(self.device)
+        if self.timing:
+            e0, e1 = self._torch.cuda.Event(enable_timing=True), self._torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+        with self._torch.cuda.device(self.device):
+            self._capi.check_lbfgs(self._lib.muse_lbfgs_advance(self._ws.data_ptr(), self.nprob, self.n, self.m, f.data_ptr(), g.data_ptr(),
+                                                                self.z_eval.data_ptr(), self._active.data_ptr(), self._stream()))
+        if self.timing:
+            e1.record(stream)
+        stream.synchronize()
+        if self.timing:
+            self.advance_ms += e0.elapsed_time(e1)
+        self.rounds += 1
+        self.syncs += 1
+        return int(self._active[0])
+
+    def result(self):
+        """(ẑ [nprob, n] -- a new tensor on the device --, records [nprob] in _capi.INFO_DTYPE)"""
+        z = self._torch.empty_like(self.z_eval)
+        with self._torch.cuda.device(self.device):
+            self._capi.check_lbfgs(self._lib.muse_lbfgs_result(self._ws.data_ptr(), self.nprob, self.n, self.m, z.data_ptr(),
+                                                               self._info.data_ptr(), self._stream()))
+        info = np.frombuffer(self._info.cpu().numpy().tobytes(), dtype=self._capi.INFO_DTYPE).copy()
+        self.syncs += 1
+        return z, info
+
+
+class BatchedTorchMuseProblem(TorchMuseProblem):
+    """TorchMuseProblem whose maps run ALL their elements at once: the closure is evaluated once per round for the whole batch -- by
+    `logLike_batched(x [B, ...], z [B, ...], theta [B, nθ]) -> [B]` (row b: element b's own θ) or, without it, by torch.func.vmap of
+    the per-simulation `logLike` -- and everything between two evaluations (L-BFGS + HagerZhang, optim.lbfgs decision for decision) is
+    one launch of libmuse_lbfgs.so's kernel for all elements, one workgroup per element.  The host reads one word per round.
+
+    The driver's batched seams (map_and_score_batch, fd_jacobian_batch, get_zhat / set_zhat, scores_in_both_spaces) follow
+    HipMuseProblem's element order and slot rule; draws are the serial class's, bit for bit.  float64 on a GPU only: no CPU fallback."""
+    supports_native_muse = False
+    MAX_ROUNDS = 200000
+
+    def __init__(self, x, sample_x_z, logLike, logPrior=None, device=None, dtype=None, logLike_batched=None):
+        super().__init__(x, sample_x_z, logLike, logPrior, device, dtype)
+        from . import _capi
+        if self.device.type != "cuda":
+            raise _capi.MuseError(-3, "no HIP device available (BatchedTorchMuseProblem runs libmuse_lbfgs's kernels: there is no CPU fallback)")
+        if self.dtype != self._torch.float64:
+            raise ValueError("BatchedTorchMuseProblem is float64 only (libmuse_lbfgs's kernels)")
+        _capi.load_lbfgs_library()
+        self._capi = _capi
+        self._batched = logLike_batched
+        self._vmapped = None
+        self._batch = None
+        self._zhat = None        # [slots, N] on the device: element e's MAP stays at slot e
+        self._zshape = None
+        self.last_rounds = self.last_syncs = 0
+
+    # -- the batched closure
+    def _logLike_rows(self, x, z, theta):
+        if self._batched is not None:
+            return self._batched(x, z, theta)
+        torch = self._torch
+        if self._vmapped is None:
+            self._vmapped = torch.func.vmap(self._logLike, in_dims=(0, 0, 0))
+        try:
+            return self._vmapped(x, z, theta)
+        except Exception as e:
+            raise ValueError("torch.func.vmap cannot trace this logLike (" + str(e).splitlines()[0] + "): pass `logLike_batched(x [B, ...], "
+                             "z [B, ...], theta [B, nθ]) -> [B]` to BatchedTorchMuseProblem") from e
+
+    def _theta_rows(self, theta, n):
+        t = self._theta(theta)
+        return t.reshape(1, -1).expand(n, -1).contiguous()
+
+    def _solve(self, X, Z0, TH, atol):
+        """MAPs of all rows: X [B, ...], Z0 [B, N] (flattened latents), TH [B, nθ] -> (ẑ [B, N], records [B])."""
+        torch = self._torch
+        B, N = Z0.shape
+        if self._batch is None or (self._batch.nprob, self._batch.n) != (B, N):
+            self._batch = LbfgsBatch(self.device, B, N)
+        batch = self._batch
+        batch.begin(Z0.contiguous(), atol)
+        while True:
+            z = batch.z_eval.view((B,) + self._zshape).detach().requires_grad_(True)
+            with torch.enable_grad():
+                f = -self._logLike_rows(X, z, TH)
+                g, = torch.autograd.grad(f.sum(), z)
+            if batch.advance(f.detach().reshape(B), g.reshape(B, N)) == 0:
+                break
+            if batch.rounds > self.MAX_ROUNDS:
+                raise RuntimeError("BatchedTorchMuseProblem: the batch did not end")
+        zhat, info = batch.result()
+        self.last_rounds, self.last_syncs = batch.rounds, batch.syncs
+        return zhat, info
+
+    def _scores(self, X, zhat, TH):
+        torch = self._torch
+        th = TH.detach().clone().requires_grad_(True)
+        with torch.enable_grad():
+            f = self._logLike_rows(X, zhat.view((zhat.shape[0],) + self._zshape).detach(), th)
+            g, = torch.autograd.grad(f.sum(), th, allow_unused=True)
+        return np.zeros(tuple(th.shape)) if g is None else g.detach().cpu().numpy().astype(np.float64)
+
+    def _draw(self, rng, sim, theta):
+        x, z = self.sample_x_z(SimRng(int(rng), int(sim)), theta)
+        if self._zshape is None:
+            self._zshape = tuple(z.shape)
+        return x, z
+
+    def _latent_shape(self, rng, theta):
+        if self._zshape is None:
+            self._draw(rng, 0, theta)
+        return self._zshape
+
+    def _slots(self, n, N):
+        torch = self._torch
+        if self._zhat is None or self._zhat.shape[1] != N:
+            self._zhat = torch.zeros((n, N), dtype=self.dtype, device=self.device)
+        elif self._zhat.shape[0] < n:
+            self._zhat = torch.cat([self._zhat, torch.zeros((n - self._zhat.shape[0], N), dtype=self.dtype, device=self.device)])
+        return self._zhat
+
+    # -- the seams muse.py looks for
+    def map_and_score_batch(self, rng, sim_begin, sim_end, theta, *, include_data=False, atol=1e-2, z0_mode=0):
+        """All elements of one muse!/get_J! map at once.  Returns (g [n, nθ], info [n]); element order: [data], sim_begin .. sim_end-1;
+        ẑ of element e stays resident (on the device) at slot e."""
+        torch, capi = self._torch, self._capi
+        rng = int(rng.seed) if isinstance(rng, SimRng) else int(rng)
+        xs, zs = [], []
+        zshape = self._latent_shape(rng, theta)
+        if include_data:
+            if self.x is None:
+                raise ValueError("include_data needs the problem's x")
+            xs.append(self.x)
+            zs.append(None)
+        for s in range(int(sim_begin), int(sim_end)):
+            x, z = self._draw(rng, s, theta)
+            xs.append(x)
+            zs.append(z)
+        n, N = len(xs), int(np.prod(zshape, dtype=np.int64))
+        X = torch.stack(xs)
+        if z0_mode == capi.Z0_WARM:
+            if self._zhat is None or self._zhat.shape[0] < n or self._zhat.shape[1] != N:
+                raise ValueError("Z0_WARM needs resident MAPs for every element (an earlier map, or set_zhat)")
+            Z0 = self._zhat[:n].clone()
+        elif z0_mode == capi.Z0_TRUE:
+            Z0 = torch.stack([torch.zeros(zshape, dtype=self.dtype, device=self.device) if z is None else z for z in zs]).reshape(n, N)
+        else:
+            Z0 = torch.zeros((n, N), dtype=self.dtype, device=self.device)
+        TH = self._theta_rows(theta, n)
+        zhat, info = self._solve(X, Z0, TH, atol)
+        self._slots(n, N)[:n] = zhat
+        return self._scores(X, zhat, TH), info
+
+    def scores_in_both_spaces(self, g, theta, theta_t):
+        """(g, g′): the transformed-space score by the chain rule through the transform, as grad_theta_logLike takes it."""
+        J = self._jac_inv_transform(np.atleast_1d(np.asarray(theta_t, dtype=np.float64)))
+        return g, g @ J
+
+    def get_zhat(self, slot_begin, slot_end):
+        if self._zhat is None or slot_end > self._zhat.shape[0]:
+            raise ValueError("no resident MAP at these slots")
+        return self._zhat[slot_begin:slot_end].cpu().numpy().astype(np.float64)
+
+    def set_zhat(self, slot_begin, zs):
+        zs = self._t(zs)
+        zs = zs.reshape(zs.shape[0], -1) if zs.dim() > 1 else zs.reshape(1, -1)
+        self._slots(slot_begin + zs.shape[0], zs.shape[1])[slot_begin:slot_begin + zs.shape[0]] = zs
+
+    def fd_jacobian_batch(self, rng, sim_begin, sim_end, theta0, step, *, atol=1e-2, fid_mode=0, fid_sim=None):
+        """get_H! by finite differences for sims [sim_begin, sim_end) (muse._fd_serial's map; include/muse_hip.h, muse_fd_jacobian_batch):
+        the fiducial MAP(s) first, then all 2 nθ nsims perturbed solves as ONE batch.  Returns (Hs [nsims, nθ, nθ],
+        info [nsims, nθ, 2]: last index 0 = plus, 1 = minus)."""
+        torch = self._torch
+        from .problem import MASTER_SIM
+        rng = int(rng.seed) if isinstance(rng, SimRng) else int(rng)
+        fid_sim = MASTER_SIM if fid_sim is None else int(fid_sim)
+        theta0 = np.atleast_1d(np.asarray(theta0, dtype=np.float64))
+        step = np.broadcast_to(np.atleast_1d(np.asarray(step, dtype=np.float64)), theta0.shape)
+        nth, sims = theta0.size, list(range(int(sim_begin), int(sim_end)))
+        zshape = self._latent_shape(rng, theta0)
+        N = int(np.prod(zshape, dtype=np.int64))
+        fids = [fid_sim] if fid_mode == 0 else sims
+        Xf = torch.stack([self._draw(rng, s, theta0)[0] for s in fids])
+        zfid, _ = self._solve(Xf, torch.zeros((len(fids), N), dtype=self.dtype, device=self.device), self._theta_rows(theta0, len(fids)), atol)
+        xs, z0 = [], []
+        for k, s in enumerate(sims):
+            for j in range(nth):
+                for sign in (1.0, -1.0):
+                    th = theta0.copy()
+                    th[j] = theta0[j] + sign * step[j]
+                    xs.append(self._draw(rng, s, th)[0])
+                    z0.append(zfid[0 if fid_mode == 0 else k])
+        X, TH = torch.stack(xs), self._theta_rows(theta0, len(xs))
+        zhat, info = self._solve(X, torch.stack(z0), TH, atol)
+        g = self._scores(X, zhat, TH).reshape(len(sims), nth, 2, nth)          # [sim, column j, plus / minus, component i]
+        cols = (-0.5 * g[:, :, 1, :] + 0.5 * g[:, :, 0, :]) / step[None, :, None]
+        return np.ascontiguousarray(np.swapaxes(cols, 1, 2)), info.reshape(len(sims), nth, 2)
+
+
 def _cg(A, b, maxiter, reltol):
     """Conjugate gradients for A y = b from y = 0 (A symmetric positive definite, given as a function): (y, iterations); stops at
     |r| <= reltol |b| or after maxiter iterations."""

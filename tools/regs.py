@@ -139,7 +139,7 @@ def library_report(path):
     rows = []
     for b in out.split("- .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", b).group(1)
-        if "map_score" not in name and "muse_loop" not in name:
+        if "map_score" not in name and "muse_loop" not in name and "muse_lbfgs" not in name:   # (libmuse_lbfgs.so: every kernel)
             continue
         g = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, b).group(1))
         short = name.replace("_ZN4muse16map_score_kernelINS_", "").replace("_ZN4muse16muse_loop_kernelINS_", "loop:").replace("EvNS_9BatchArgsE", "")
