@@ -24,6 +24,30 @@
  * problem's z_eval row stays at its final point (the objective keeps seeing finite input), its record no longer changes and the
  * values passed for it are ignored.
  *
+ * A second reverse-communication solver of the same build: lock-step CONJUGATE GRADIENTS for a batch of rows, each one linear system
+ * M y = b with M symmetric positive definite and APPLIED BY THE CALLER (get_H! by implicit differentiation for closure problems: M is
+ * minus the Hessian of logLike in z at a simulation's MAP, a double backward pass of the caller's closure; one row per simulation and
+ * column).  Once per round the caller evaluates M p for all rows as one [nrows][n] batch; everything between two evaluations -- p.Mp,
+ * the guard, the updates of y and r, r.r, the stopping rule, the next direction -- is one launch, one workgroup per row.  Plain CG from
+ * y = 0 in the order of IterativeSolvers' cg without a preconditioner; a row stops at |r|_2 <= max(reltol |b|_2, abstol) (the
+ * recurrence residual) or after maxiter iterations.
+ *
+ *     bytes = muse_lbfgs_cg_workspace_bytes(nrows, n);                  ws: that many bytes of device memory, 256-byte aligned
+ *     muse_lbfgs_cg_begin(ws, nrows, n, b, reltol, abstol, maxiter, p_eval, active, stream);      synchronise the stream
+ *     while (*active > 0) {
+ *         Mp[r][:] = M_r p_eval[r][:]                                                  (the caller's, for every row r)
+ *         muse_lbfgs_cg_advance(ws, nrows, n, Mp, p_eval, active, stream);
+ *         synchronise the stream
+ *     }
+ *     muse_lbfgs_cg_result(ws, nrows, n, y_out, iterations_out, resnorm_out, stream);
+ *
+ * b, p_eval, Mp, y_out: [nrows][n] doubles in device memory, dense rows as above; p_eval overlaps neither b nor Mp.  The direction p
+ * lives in p_eval and nowhere else: the caller must leave it as the library wrote it.  The same contract: no state but the workspace,
+ * nothing allocates, synchronises or reads the device, the shape is an argument of every call, a row's result depends on its own
+ * inputs and n only.  A finished row's p_eval row stays where it is (the operator keeps seeing finite input) and what is passed for it
+ * is ignored.  A row whose p.Mp is not positive or not finite -- M is not positive definite there -- stops with y as it was and the
+ * count -1 - iterations (include/muse_hip.h's convention for the implicit get_H!).
+ *
  * Every function returns 0, or a negative number: MUSE_LBFGS_BAD_ARGUMENT, or -(100 + the hipError_t of a failed launch).
  */
 #ifndef MUSE_LBFGS_H
@@ -58,6 +82,25 @@ int muse_lbfgs_result(void* ws, int64_t nprob, int64_t n, int m, double* z_out, 
 
 /* the advance kernel's workgroup size for rows of length n (a function of n alone) */
 int muse_lbfgs_workgroup_size(int64_t n);
+
+/* ---- lock-step conjugate gradients (the shape limits and the workgroup size are those above) ---- */
+
+/* the workspace's size in bytes: one record per row and [nrows][2][n] doubles, y and r (negative: a bad argument) */
+int64_t muse_lbfgs_cg_workspace_bytes(int64_t nrows, int64_t n);
+
+/* start nrows systems with right-hand sides b: y = 0, r = b, the first direction (b itself) into p_eval, the tolerance
+ * max(reltol |b|, abstol); a row with b = 0 (or within abstol) or maxiter == 0 is finished at once with count 0.  *active_out as for
+ * muse_lbfgs_advance */
+int muse_lbfgs_cg_begin(void* ws, int64_t nrows, int64_t n, const double* b, double reltol, double abstol, int maxiter, double* p_eval,
+                        int* active_out, void* stream);
+
+/* one round: consumes Mp = M p_eval, writes the next direction of every active row into p_eval and the number of rows still active to
+ * *active_out */
+int muse_lbfgs_cg_advance(void* ws, int64_t nrows, int64_t n, const double* Mp, double* p_eval, int* active_out, void* stream);
+
+/* the solutions y_out [nrows][n], the counts iterations_out [nrows] (int32; negative: -1 - iterations, the guard stopped the row) and
+ * resnorm_out [nrows], the recurrence residual |r|_2 (all device memory) */
+int muse_lbfgs_cg_result(void* ws, int64_t nrows, int64_t n, double* y_out, int32_t* iterations_out, double* resnorm_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -156,6 +156,11 @@ LBFGS_SIGNATURES = {
     "muse_lbfgs_advance": (_i, [_vp, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
     "muse_lbfgs_result": (_i, [_vp, _i64, _i64, _i, _vp, _vp, _vp]),
     "muse_lbfgs_workgroup_size": (_i, [_i64]),
+    # the lock-step conjugate gradients (rows M y = b, M applied by the caller)
+    "muse_lbfgs_cg_workspace_bytes": (_i64, [_i64, _i64]),
+    "muse_lbfgs_cg_begin": (_i, [_vp, _i64, _i64, _vp, _d, _d, _i, _vp, _vp, _vp]),
+    "muse_lbfgs_cg_advance": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "muse_lbfgs_cg_result": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
 }
 _lbfgs_lib = None
 

@@ -187,8 +187,9 @@ LBFGS_DIR = os.path.join(_HERE, "lbfgs")
 LBFGS_LIB_PATH = os.path.join(_HERE, "libmuse_lbfgs.so")
 _LBFGS_API = os.path.join(INCLUDE_DIR, "muse_lbfgs.h")
 _LBFGS_SOURCE = os.path.join(LBFGS_DIR, "lbfgs_kernels.hip")
-_LBFGS_DEPS = [_LBFGS_SOURCE, os.path.join(LBFGS_DIR, "lbfgs_control.hpp"), os.path.join(LBFGS_DIR, "lbfgs_advance.hpp"), _LBFGS_API,
-               os.path.join(CSRC, "reduce.hpp"), os.path.join(CSRC, "args.hpp")]
+_LBFGS_DEPS = [_LBFGS_SOURCE, os.path.join(LBFGS_DIR, "lbfgs_control.hpp"), os.path.join(LBFGS_DIR, "lbfgs_advance.hpp"),
+               os.path.join(LBFGS_DIR, "cg_control.hpp"), os.path.join(LBFGS_DIR, "cg_advance.hpp"), os.path.join(LBFGS_DIR, "cg_kernels.hpp"),
+               _LBFGS_API, os.path.join(CSRC, "reduce.hpp"), os.path.join(CSRC, "args.hpp")]
 
 
 def lbfgs_declared_symbols():

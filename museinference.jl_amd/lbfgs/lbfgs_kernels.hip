@@ -338,3 +338,6 @@ int muse_lbfgs_result(void* ws, int64_t nprob, int64_t n, int m, double* z_out, 
 int muse_lbfgs_workgroup_size(int64_t n) { return n <= kSmallMaxN ? kSmallT : kLargeT; }
 
 }  // extern "C"
+
+// muse_lbfgs_cg_*: the lock-step conjugate gradients, kernels and entry points (the same workgroup sizes, shape limits and helpers)
+#include "cg_kernels.hpp"

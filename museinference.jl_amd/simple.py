@@ -258,6 +258,89 @@ class LbfgsBatch:
         return z, info
 
 
+class CgBatch:
+    """libmuse_lbfgs.so's lock-step conjugate gradients (include/muse_lbfgs.h, muse_lbfgs_cg_*) for one batch shape [nrows, n] on a GPU:
+    row r is one system M_r y = b_r whose operator the caller applies.  The workspace, the direction rows and the word the kernel
+    reports into are allocated once, as torch tensors; every launch goes to torch's current stream.
+
+        active = cg.begin(b, reltol, abstol, maxiter);  while active: Mp = M applied to cg.p_eval -> active = cg.advance(Mp);  cg.result()
+
+    The direction lives in `p_eval` and nowhere else: read it, never write it.
+    """
+
+    def __init__(self, device, nrows, n):
+        import torch
+        from . import _capi
+        self._torch, self._capi, self._lib = torch, _capi, _capi.load_lbfgs_library()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _capi.MuseError(-3, "no HIP device available (libmuse_lbfgs has no CPU fallback)")
+        self.nrows, self.n = int(nrows), int(n)
+        nbytes = _capi.check_lbfgs(self._lib.muse_lbfgs_cg_workspace_bytes(self.nrows, self.n))
+        self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.p_eval = torch.zeros((self.nrows, self.n), dtype=torch.float64, device=self.device)
+        self._active = torch.zeros(1, dtype=torch.int32).pin_memory()
+        self._its = torch.empty(self.nrows, dtype=torch.int32, device=self.device)
+        self._res = torch.empty(self.nrows, dtype=torch.float64, device=self.device)
+        self.rounds = self.syncs = 0
+        self.timing, self.advance_ms = False, 0.0      # timing: device time of the advance launches, summed (tools/closures_implicit_bench.py)
+
+    def _stream(self):
+        return self._torch.cuda.current_stream(self.device).cuda_stream
+
+    def _rows(self, t):
+        torch = self._torch
+        if not (torch.is_tensor(t) and t.device == self.p_eval.device and t.dtype == torch.float64 and tuple(t.shape) == (self.nrows, self.n)):
+            raise ValueError(f"expected a float64 tensor of shape {(self.nrows, self.n)} on {self.p_eval.device}")
+        if t.data_ptr() == self.p_eval.data_ptr():
+            raise ValueError("p_eval is the solver's own: pass a tensor of the caller's")
+        return t.contiguous()
+
+    def _wait(self):
+        self._torch.cuda.current_stream(self.device).synchronize()
+        self.syncs += 1
+        return int(self._active[0])
+
+    def begin(self, b, reltol, abstol=0.0, maxiter=100):
+        """Start every row at y = 0 with right-hand side b [nrows, n]; p_eval = b.  Returns the number of active rows (one synchronisation)."""
+        b = self._rows(b)
+        self.rounds = self.syncs = 0
+        self.advance_ms = 0.0
+        with self._torch.cuda.device(self.device):
+            self._capi.check_lbfgs(self._lib.muse_lbfgs_cg_begin(self._ws.data_ptr(), self.nrows, self.n, b.data_ptr(), float(reltol), float(abstol),
+                                                                 int(maxiter), self.p_eval.data_ptr(), self._active.data_ptr(), self._stream()))
+        return self._wait()
+
+    def advance(self, Mp):
+        """One round: Mp [nrows, n] = M applied to p_eval.  Returns the number of rows still active (the round's ONE synchronisation)."""
+        Mp = self._rows(Mp)
+        stream = self._torch.cuda.current_stream(self.device)
+        if self.timing:
+            e0, e1 = self._torch.cuda.Event(enable_timing=True), self._torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+        with self._torch.cuda.device(self.device):
+            self._capi.check_lbfgs(self._lib.muse_lbfgs_cg_advance(self._ws.data_ptr(), self.nrows, self.n, Mp.data_ptr(), self.p_eval.data_ptr(),
+                                                                   self._active.data_ptr(), self._stream()))
+        if self.timing:
+            e1.record(stream)
+        active = self._wait()
+        if self.timing:
+            self.advance_ms += e0.elapsed_time(e1)
+        self.rounds += 1
+        return active
+
+    def result(self):
+        """(y [nrows, n] -- a new tensor on the device --, counts [nrows] int32 (negative: -1 - iterations, the guard stopped the row),
+        |r| [nrows], the recurrence residual; the last two on the host)"""
+        y = self._torch.empty_like(self.p_eval)
+        with self._torch.cuda.device(self.device):
+            self._capi.check_lbfgs(self._lib.muse_lbfgs_cg_result(self._ws.data_ptr(), self.nrows, self.n, y.data_ptr(), self._its.data_ptr(),
+                                                                  self._res.data_ptr(), self._stream()))
+        its, res = self._its.cpu().numpy().copy(), self._res.cpu().numpy().copy()
+        self.syncs += 1
+        return y, its, res
+
+
 class BatchedTorchMuseProblem(TorchMuseProblem):
     """TorchMuseProblem whose maps run ALL their elements at once: the closure is evaluated once per round for the whole batch -- by
     `logLike_batched(x [B, ...], z [B, ...], theta [B, nθ]) -> [B]` (row b: element b's own θ) or, without it, by torch.func.vmap of
@@ -268,6 +351,7 @@ class BatchedTorchMuseProblem(TorchMuseProblem):
     HipMuseProblem's element order and slot rule; draws are the serial class's, bit for bit.  float64 on a GPU only: no CPU fallback."""
     supports_native_muse = False
     MAX_ROUNDS = 200000
+    IMPLICIT_MAX_ELEMS = 1 << 24     # implicit_H_batch: simulations per chunk so that (rows = nsims nθ) x N stays at or below this
 
     def __init__(self, x, sample_x_z, logLike, logPrior=None, device=None, dtype=None, logLike_batched=None):
         super().__init__(x, sample_x_z, logLike, logPrior, device, dtype)
@@ -284,6 +368,11 @@ class BatchedTorchMuseProblem(TorchMuseProblem):
         self._zhat = None        # [slots, N] on the device: element e's MAP stays at slot e
         self._zshape = None
         self.last_rounds = self.last_syncs = 0
+        self._cg_batch = None
+        self.cg_timing = False       # implicit_H_batch: sum the device time of the CG advance launches into last_cg_advance_ms
+        self.last_cg_rounds = self.last_cg_syncs = self.last_cg_chunks = 0
+        self.last_cg_advance_ms = 0.0
+        self.last_fiducial_info = None
 
     # -- the batched closure
     def _logLike_rows(self, x, z, theta):
@@ -426,6 +515,111 @@ class BatchedTorchMuseProblem(TorchMuseProblem):
         g = self._scores(X, zhat, TH).reshape(len(sims), nth, 2, nth)          # [sim, column j, plus / minus, component i]
         cols = (-0.5 * g[:, :, 1, :] + 0.5 * g[:, :, 0, :]) / step[None, :, None]
         return np.ascontiguousarray(np.swapaxes(cols, 1, 2)), info.reshape(len(sims), nth, 2)
+
+    # -- get_H! by implicit differentiation, all simulations at once
+    def implicit_H_batch(self, seed, sim_begin, sim_end, theta0, atol=1e-1, cg_maxiter=100, cg_reltol=1.4901161193847656e-08, cg_abstol=0.0,
+                         H1_is_zero=False):
+        """The serial class's implicit_H_batch (H = H1 - dFdθᵀ A⁻¹ dFdθ1 per simulation, see there) with every step taken for all
+        simulations at once: the fiducial MAPs are one lock-step L-BFGS batch, the derivative terms one autograd pass per θ component
+        over the whole batch, and the nsims nθ linear solves one lock-step conjugate-gradient batch of libmuse_lbfgs.so (CgBatch: one
+        workgroup per (simulation, column), the operator one double backward of the batched closure per round, one word read per round).
+        cg_abstol and H1_is_zero are IterativeSolvers' abstol and the reference's implicit_diff_H1_is_zero.  Simulations are taken in
+        chunks of at most IMPLICIT_MAX_ELEMS / (nθ N); rows are independent.  Returns (Hs [n, nθ, nθ], CG counts [n, nθ]: negative,
+        -1 - iterations, where p.Ap was not positive -- the Hessian in z is not negative definite at that fiducial MAP)."""
+        seed = int(seed.seed) if isinstance(seed, SimRng) else int(seed)
+        theta0 = np.atleast_1d(np.asarray(theta0, dtype=np.float64))
+        sims = list(range(int(sim_begin), int(sim_end)))
+        nt = theta0.size
+        N = int(np.prod(self._latent_shape(seed, theta0), dtype=np.int64))
+        per = max(1, int(self.IMPLICIT_MAX_ELEMS) // max(1, nt * N))
+        self.last_cg_rounds = self.last_cg_syncs = self.last_cg_chunks = 0
+        self.last_cg_advance_ms = 0.0
+        Hs, its, infos = [], [], []
+        for c in range(0, len(sims), per):
+            H, k, info = self._implicit_chunk(seed, sims[c:c + per], theta0, atol, cg_maxiter, cg_reltol, cg_abstol, H1_is_zero)
+            Hs.append(H)
+            its.append(k)
+            infos.append(info)
+        self.last_fiducial_info = np.concatenate(infos) if infos else None
+        if not Hs:
+            return np.zeros((0, nt, nt)), np.zeros((0, nt), dtype=np.int32)
+        return np.concatenate(Hs), np.concatenate(its)
+
+    def _implicit_chunk(self, seed, sims, theta0, atol, cg_maxiter, cg_reltol, cg_abstol, H1_is_zero):
+        torch = self._torch
+        S, nt = len(sims), theta0.size
+        xs = [self._draw(seed, s, theta0)[0] for s in sims]          # the serial class's draws, bit for bit
+        zshape = self._zshape
+        N = int(np.prod(zshape, dtype=np.int64))
+        X, TH = torch.stack(xs), self._theta_rows(theta0, S)
+        zhat, info = self._solve(X, torch.zeros((S, N), dtype=self.dtype, device=self.device), TH, atol)     # (zhat_guess_from_truth: zeros)
+        zhat = zhat.detach()
+        R = S * nt
+        with torch.enable_grad():
+            # the draws again, as functions of each simulation's own θ (the generator re-seeded: the same random numbers)
+            th_draw = TH.clone().requires_grad_(True)
+            xg = []
+            for i, s in enumerate(sims):
+                gen = torch.Generator(device=self.device)
+                gen.manual_seed(self._stream(SimRng(seed, s)))
+                xg.append(self._sample(gen, th_draw[i])[0].to(self.dtype))
+            Xg = torch.stack(xg)
+            zfix = zhat.view((S,) + zshape)
+            # H1[s, i, j] = ∂/∂θ_j of the score's component i through the draw: nθ backward passes, each over every simulation
+            H1 = torch.zeros((S, nt, nt), dtype=self.dtype, device=self.device)
+            if not H1_is_zero and Xg.requires_grad:
+                th_score = TH.clone().requires_grad_(True)
+                score, = torch.autograd.grad(self._logLike_rows(Xg, zfix, th_score).sum(), th_score, create_graph=True, allow_unused=True)
+                if score is not None and score.requires_grad:
+                    for i in range(nt):
+                        row, = torch.autograd.grad(score[:, i].sum(), th_draw, retain_graph=True, allow_unused=True)
+                        if row is not None:
+                            H1[:, i, :] = row
+            # dFdθ1 = ∂θ ∇z logLike(x(θ), ẑ, θ0), column by column in forward mode (the double-backward identity: w = Jᵀ v is linear in v,
+            # so ∂(w_j)/∂v = J e_j): nθ passes over every simulation, never one per latent component
+            b = torch.zeros((S, nt, N), dtype=self.dtype, device=self.device)
+            if Xg.requires_grad:
+                zz = zfix.clone().requires_grad_(True)
+                gz, = torch.autograd.grad(self._logLike_rows(Xg, zz, TH).sum(), zz, create_graph=True)
+                if gz.requires_grad:
+                    v = torch.zeros_like(gz).requires_grad_(True)
+                    w, = torch.autograd.grad(gz, th_draw, grad_outputs=v, create_graph=True, allow_unused=True)
+                    if w is not None and w.requires_grad:
+                        for j in range(nt):
+                            col, = torch.autograd.grad(w[:, j].sum(), v, retain_graph=True, allow_unused=True)
+                            if col is not None:
+                                b[:, j, :] = -col.reshape(S, N)
+            del xg, Xg
+            # the R = S nθ systems (-A) y = b: row (s, j) sees simulation s's x and ẑ, so one double backward of the batched closure is
+            # every row's own Hessian-vector product
+            XR, THR = X.repeat_interleave(nt, dim=0), self._theta_rows(theta0, R)
+            ZR = zhat.repeat_interleave(nt, dim=0).view((R,) + zshape).clone().requires_grad_(True)
+            g, = torch.autograd.grad(self._logLike_rows(XR, ZR, THR).sum(), ZR, create_graph=True)
+            if self._cg_batch is None or (self._cg_batch.nrows, self._cg_batch.n) != (R, N):
+                self._cg_batch = CgBatch(self.device, R, N)
+            cg = self._cg_batch
+            cg.timing = self.cg_timing
+            active = cg.begin(b.reshape(R, N), cg_reltol, cg_abstol, cg_maxiter)
+            while active > 0:
+                Ap, = torch.autograd.grad(g, ZR, cg.p_eval.view_as(g), retain_graph=True)
+                active = cg.advance(-Ap.reshape(R, N))
+                if cg.rounds > max(int(cg_maxiter), 0):
+                    raise RuntimeError("BatchedTorchMuseProblem: the conjugate-gradient batch did not end")
+            Y, counts, _ = cg.result()
+            del g
+            # H2 = -dFdθᵀ Y without forming dFdθ: one backward pass with respect to every row's own θ
+            thR = THR.clone().requires_grad_(True)
+            z2 = ZR.detach().requires_grad_(True)
+            gz2, = torch.autograd.grad(self._logLike_rows(XR, z2, thR).sum(), z2, create_graph=True)
+            dth, = torch.autograd.grad((gz2.reshape(R, N) * Y).sum(), thR, allow_unused=True)
+        H = H1
+        if dth is not None:
+            H = H1 - dth.reshape(S, nt, nt).transpose(1, 2)        # dth[(s, j), i] = (dFdθᵀ y_sj)_i = H2[s, i, j]
+        self.last_cg_rounds += cg.rounds
+        self.last_cg_syncs += cg.syncs
+        self.last_cg_chunks += 1
+        self.last_cg_advance_ms += cg.advance_ms
+        return H.detach().cpu().numpy().astype(np.float64), counts.reshape(S, nt).astype(np.int32), info
 
 
 def _cg(A, b, maxiter, reltol):
