@@ -102,6 +102,26 @@ int muse_lbfgs_cg_advance(void* ws, int64_t nrows, int64_t n, const double* Mp, 
  * resnorm_out [nrows], the recurrence residual |r|_2 (all device memory) */
 int muse_lbfgs_cg_result(void* ws, int64_t nrows, int64_t n, double* y_out, int32_t* iterations_out, double* resnorm_out, void* stream);
 
+/* ---- the engine's normal stream, for all rows of a map in one launch ----
+ *
+ * The stream of (seed, sim) is the engine's (include/muse_hip.h; csrc/rng.hpp): Philox4x32-10 keyed by the seed with the counter
+ * (element, sim), and a fixed-sequence Box-Muller that gives element i the pair (n1(i), n2(i)) = normal_pair(seed, sim, i).  As a
+ * SEQUENCE e_0, e_1, ... it is
+ *
+ *     e_{2i} = n1(i),   e_{2i+1} = n2(i).
+ *
+ * A request for k values returns the next k values and starts at a pair boundary: the cursor, counted in pairs, advances by
+ * ceil(k / 2), and an odd request discards its last n2.  The stream is a pure function of (seed, sim, i) -- it is never advanced by
+ * the library; the cursor is the caller's, passed as pair_offset -- so a simulation's numbers are the same alone or in any batch,
+ * and bit-equal to what the engine gives that simulation's elements.
+ *
+ * out[r][j] = e_{2*pair_offset + j} of stream (seed, sims[r]) for j < count.
+ * out: [nrows][count] doubles in device memory, dense rows (stride count; any 8-byte alignment).  sims: [nrows] int64 in device
+ * memory, every one non-negative (the package's MASTER_SIM = 2^62 - 1 and DATA_SIM = 2^32 - 1 included).  A bad argument: a null out
+ * or sims, nrows < 1, count < 1, pair_offset < 0, nrows * ceil(count / 2048) above 2^31 - 1, pair_offset + ceil(count / 2) above
+ * 2^63 - 1.  The same contract as above: no state, no allocation, no synchronisation, no read of the device; one launch, to `stream`. */
+int muse_lbfgs_normals(double* out, int64_t nrows, int64_t count, uint64_t seed, const int64_t* sims, int64_t pair_offset, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -341,3 +341,6 @@ int muse_lbfgs_workgroup_size(int64_t n) { return n <= kSmallMaxN ? kSmallT : kL
 
 // muse_lbfgs_cg_*: the lock-step conjugate gradients, kernels and entry points (the same workgroup sizes, shape limits and helpers)
 #include "cg_kernels.hpp"
+
+// muse_lbfgs_normals: the engine's normal stream for all rows of a map in one launch (the batched closure problems' draws)
+#include "normals_kernels.hpp"

@@ -341,6 +341,57 @@ class CgBatch:
         return y, its, res
 
 
+class EngineNormals:
+    """The ENGINE's normal streams (csrc/rng.hpp; include/muse_lbfgs.h, muse_lbfgs_normals) for a batch of simulations: row b draws from
+    stream (seed, sims[b]) -- the numbers HipMuseProblem gives that simulation's elements, and oracle.normals, bit for bit.  A stream
+    as a sequence is e_2i = n1(i), e_2i+1 = n2(i); a request for k values per row returns the next k and starts at a pair boundary:
+    the cursor (in pairs, the same for every row) advances by ceil(k / 2), an odd request discards its last n2.
+
+        normals = EngineNormals(device, seed, sims);   e = normals(N, 2)        # e[b, i] = (n1(i), n2(i)) of simulation sims[b]
+
+    Every request is ONE launch for all rows on torch's current stream.  The result is a new float64 tensor and is not differentiable
+    (the numbers do not depend on θ).  A GPU only: no CPU fallback."""
+
+    def __init__(self, device, seed, sims):
+        import torch
+        from . import _capi
+        self._torch, self._capi, self._lib = torch, _capi, _capi.load_lbfgs_library()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _capi.MuseError(-3, "no HIP device available (libmuse_lbfgs has no CPU fallback)")
+        self.seed = int(seed) % (1 << 64)
+        s = sims.detach().cpu().numpy() if torch.is_tensor(sims) else np.asarray(sims)
+        s = np.ascontiguousarray(np.atleast_1d(s).astype(np.int64).reshape(-1))
+        if s.size < 1 or s.min() < 0:
+            raise ValueError("EngineNormals: at least one simulation index, every one non-negative")
+        self.sims = torch.as_tensor(s, device=self.device)
+        self.B = int(s.size)
+        self.cursor = 0          # in pairs
+
+    def normals(self, *shape):
+        """[B, *shape] float64: row b holds the next prod(shape) values of stream (seed, sims[b])."""
+        torch = self._torch
+        shape = tuple(int(k) for k in shape)
+        count = int(np.prod(shape, dtype=np.int64))
+        if not shape or any(k < 1 for k in shape):
+            raise ValueError("EngineNormals: every dimension of a request is at least 1")
+        out = torch.empty((self.B,) + shape, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._capi.check_lbfgs(self._lib.muse_lbfgs_normals(out.data_ptr(), self.B, count, self.seed, self.sims.data_ptr(), self.cursor,
+                                                                torch.cuda.current_stream(self.device).cuda_stream))
+        self.cursor += (count + 1) // 2
+        return out
+
+    __call__ = normals
+
+    def fresh(self):
+        """The same streams from their start: a new object (cursor 0) over the same device tensor of simulation indices."""
+        other = object.__new__(EngineNormals)
+        other.__dict__.update(self.__dict__)
+        other.cursor = 0
+        return other
+
+
 class BatchedTorchMuseProblem(TorchMuseProblem):
     """TorchMuseProblem whose maps run ALL their elements at once: the closure is evaluated once per round for the whole batch -- by
     `logLike_batched(x [B, ...], z [B, ...], theta [B, nθ]) -> [B]` (row b: element b's own θ) or, without it, by torch.func.vmap of
@@ -348,12 +399,23 @@ class BatchedTorchMuseProblem(TorchMuseProblem):
     one launch of libmuse_lbfgs.so's kernel for all elements, one workgroup per element.  The host reads one word per round.
 
     The driver's batched seams (map_and_score_batch, fd_jacobian_batch, get_zhat / set_zhat, scores_in_both_spaces) follow
-    HipMuseProblem's element order and slot rule; draws are the serial class's, bit for bit.  float64 on a GPU only: no CPU fallback."""
+    HipMuseProblem's element order and slot rule; draws are the serial class's, bit for bit.  float64 on a GPU only: no CPU fallback.
+
+    With `sample_x_z_batched(normals, theta [B, nθ]) -> (x [B, ...], z [B, ...])` the draws of a map are batched too: `normals` is an
+    EngineNormals over the map's rows (`normals(*shape)` -> [B, *shape] standard normals, row b from the engine's stream of row b's
+    simulation), row b uses its own θ row as in logLike_batched, and a map draws all its rows in one call -- every request one launch,
+    no generator seeded per simulation.  The random numbers are then the ENGINE's: a closure restatement of a header model sees exactly
+    HipMuseProblem's simulations.  A sampler must request the same shapes in the same order at every θ (a simulation then keeps its
+    random numbers across θ, which the finite-difference and the implicit get_H! rely on), and must be written with differentiable
+    torch operations for implicit_H_batch.  `sample_x_z` may then be None: the per-simulation seam sample_x_z(rng, θ) is the batched
+    sampler with one row, so a simulation's draw is the same bits alone or in any batch."""
     supports_native_muse = False
     MAX_ROUNDS = 200000
     IMPLICIT_MAX_ELEMS = 1 << 24     # implicit_H_batch: simulations per chunk so that (rows = nsims nθ) x N stays at or below this
 
-    def __init__(self, x, sample_x_z, logLike, logPrior=None, device=None, dtype=None, logLike_batched=None):
+    def __init__(self, x, sample_x_z, logLike, logPrior=None, device=None, dtype=None, logLike_batched=None, sample_x_z_batched=None):
+        if sample_x_z is None and sample_x_z_batched is None:
+            raise ValueError("BatchedTorchMuseProblem needs sample_x_z or sample_x_z_batched")
         super().__init__(x, sample_x_z, logLike, logPrior, device, dtype)
         from . import _capi
         if self.device.type != "cuda":
@@ -363,6 +425,7 @@ class BatchedTorchMuseProblem(TorchMuseProblem):
         _capi.load_lbfgs_library()
         self._capi = _capi
         self._batched = logLike_batched
+        self._sample_batched = sample_x_z_batched
         self._vmapped = None
         self._batch = None
         self._zhat = None        # [slots, N] on the device: element e's MAP stays at slot e
@@ -420,6 +483,38 @@ class BatchedTorchMuseProblem(TorchMuseProblem):
             g, = torch.autograd.grad(f.sum(), th, allow_unused=True)
         return np.zeros(tuple(th.shape)) if g is None else g.detach().cpu().numpy().astype(np.float64)
 
+    # -- the batched sampler: all rows of a map in one call, the engine's streams
+    def sample_x_z(self, rng, theta):
+        """The per-simulation seam.  With sample_x_z_batched: that sampler with ONE row (the engine's stream (seed, sim)), so a
+        simulation's draw is the same bits here and in any batch; without it, the serial class's."""
+        if self._sample_batched is None:
+            return super().sample_x_z(rng, theta)
+        rng = rng if isinstance(rng, SimRng) else SimRng(int(rng), 0)
+        X, Z = self._draw_rows(EngineNormals(self.device, rng.seed, [rng.sim]), self._theta(theta).reshape(1, -1))
+        return X[0], Z[0]
+
+    def _draw_rows(self, normals, TH):
+        """(x [B, ...], z [B, ...]) of the batched sampler: row b is simulation normals.sims[b] at TH[b].  Differentiable in TH where TH
+        requires grad (and the sampler is written so); otherwise plain tensors."""
+        torch = self._torch
+        with torch.set_grad_enabled(bool(TH.requires_grad)):
+            x, z = self._sample_batched(normals, TH)
+        B = normals.B
+        if not (torch.is_tensor(x) and torch.is_tensor(z) and x.shape[:1] == (B,) and z.shape[:1] == (B,)):
+            raise ValueError(f"sample_x_z_batched must return (x [B, ...], z [B, ...]) with B = {B} rows")
+        x, z = x.to(self.device, self.dtype), z.to(self.device, self.dtype)
+        if self._zshape is None:
+            self._zshape = tuple(z.shape[1:])
+        return x, z
+
+    def _draw_sims(self, seed, sims, TH):
+        """_draw_rows over fresh streams of `sims` (one per row of TH)."""
+        return self._draw_rows(EngineNormals(self.device, seed, sims), TH)
+
+    def _theta_rows_of(self, rows):
+        """[R, nθ] on the device from a numpy array of θ rows"""
+        return self._torch.as_tensor(np.ascontiguousarray(rows, dtype=np.float64), device=self.device).to(self.dtype)
+
     def _draw(self, rng, sim, theta):
         x, z = self.sample_x_z(SimRng(int(rng), int(sim)), theta)
         if self._zshape is None:
@@ -452,10 +547,16 @@ class BatchedTorchMuseProblem(TorchMuseProblem):
                 raise ValueError("include_data needs the problem's x")
             xs.append(self.x)
             zs.append(None)
-        for s in range(int(sim_begin), int(sim_end)):
-            x, z = self._draw(rng, s, theta)
-            xs.append(x)
-            zs.append(z)
+        sims = range(int(sim_begin), int(sim_end))
+        if self._sample_batched is not None and len(sims) > 0:          # every simulation's draw in one call
+            Xs, Zs = self._draw_sims(rng, list(sims), self._theta_rows(theta, len(sims)))
+            xs.extend(Xs.unbind(0))
+            zs.extend(Zs.unbind(0))
+        else:
+            for s in sims:
+                x, z = self._draw(rng, s, theta)
+                xs.append(x)
+                zs.append(z)
         n, N = len(xs), int(np.prod(zshape, dtype=np.int64))
         X = torch.stack(xs)
         if z0_mode == capi.Z0_WARM:
@@ -500,18 +601,31 @@ class BatchedTorchMuseProblem(TorchMuseProblem):
         zshape = self._latent_shape(rng, theta0)
         N = int(np.prod(zshape, dtype=np.int64))
         fids = [fid_sim] if fid_mode == 0 else sims
-        Xf = torch.stack([self._draw(rng, s, theta0)[0] for s in fids])
+        if self._sample_batched is not None:
+            Xf = self._draw_sims(rng, fids, self._theta_rows(theta0, len(fids)))[0]
+        else:
+            Xf = torch.stack([self._draw(rng, s, theta0)[0] for s in fids])
         zfid, _ = self._solve(Xf, torch.zeros((len(fids), N), dtype=self.dtype, device=self.device), self._theta_rows(theta0, len(fids)), atol)
-        xs, z0 = [], []
-        for k, s in enumerate(sims):
+        if self._sample_batched is not None:
+            # all 2 nθ nsims perturbed draws in one call: row (k, j, sign) is simulation sims[k] at θ0 ± step_j e_j
+            thp = np.tile(theta0, (len(sims), nth, 2, 1))
             for j in range(nth):
-                for sign in (1.0, -1.0):
-                    th = theta0.copy()
-                    th[j] = theta0[j] + sign * step[j]
-                    xs.append(self._draw(rng, s, th)[0])
-                    z0.append(zfid[0 if fid_mode == 0 else k])
-        X, TH = torch.stack(xs), self._theta_rows(theta0, len(xs))
-        zhat, info = self._solve(X, torch.stack(z0), TH, atol)
+                thp[:, j, 0, j] = theta0[j] + step[j]
+                thp[:, j, 1, j] = theta0[j] - step[j]
+            X = self._draw_sims(rng, np.repeat(np.asarray(sims, dtype=np.int64), 2 * nth), self._theta_rows_of(thp.reshape(-1, nth)))[0]
+            Z0 = (zfid[:1].expand(X.shape[0], N) if fid_mode == 0 else zfid.repeat_interleave(2 * nth, dim=0)).contiguous()
+        else:
+            xs, z0 = [], []
+            for k, s in enumerate(sims):
+                for j in range(nth):
+                    for sign in (1.0, -1.0):
+                        th = theta0.copy()
+                        th[j] = theta0[j] + sign * step[j]
+                        xs.append(self._draw(rng, s, th)[0])
+                        z0.append(zfid[0 if fid_mode == 0 else k])
+            X, Z0 = torch.stack(xs), torch.stack(z0)
+        TH = self._theta_rows(theta0, X.shape[0])
+        zhat, info = self._solve(X, Z0, TH, atol)
         g = self._scores(X, zhat, TH).reshape(len(sims), nth, 2, nth)          # [sim, column j, plus / minus, component i]
         cols = (-0.5 * g[:, :, 1, :] + 0.5 * g[:, :, 0, :]) / step[None, :, None]
         return np.ascontiguousarray(np.swapaxes(cols, 1, 2)), info.reshape(len(sims), nth, 2)
@@ -548,10 +662,14 @@ class BatchedTorchMuseProblem(TorchMuseProblem):
     def _implicit_chunk(self, seed, sims, theta0, atol, cg_maxiter, cg_reltol, cg_abstol, H1_is_zero):
         torch = self._torch
         S, nt = len(sims), theta0.size
-        xs = [self._draw(seed, s, theta0)[0] for s in sims]          # the serial class's draws, bit for bit
+        TH = self._theta_rows(theta0, S)
+        if self._sample_batched is not None:
+            normals = EngineNormals(self.device, seed, sims)
+            X = self._draw_rows(normals, TH)[0]                          # every simulation's draw in one call
+        else:
+            X = torch.stack([self._draw(seed, s, theta0)[0] for s in sims])          # the serial class's draws, bit for bit
         zshape = self._zshape
         N = int(np.prod(zshape, dtype=np.int64))
-        X, TH = torch.stack(xs), self._theta_rows(theta0, S)
         zhat, info = self._solve(X, torch.zeros((S, N), dtype=self.dtype, device=self.device), TH, atol)     # (zhat_guess_from_truth: zeros)
         zhat = zhat.detach()
         R = S * nt
@@ -559,11 +677,14 @@ class BatchedTorchMuseProblem(TorchMuseProblem):
             # the draws again, as functions of each simulation's own θ (the generator re-seeded: the same random numbers)
             th_draw = TH.clone().requires_grad_(True)
             xg = []
-            for i, s in enumerate(sims):
-                gen = torch.Generator(device=self.device)
-                gen.manual_seed(self._stream(SimRng(seed, s)))
-                xg.append(self._sample(gen, th_draw[i])[0].to(self.dtype))
-            Xg = torch.stack(xg)
+            if self._sample_batched is not None:
+                Xg = self._draw_rows(normals.fresh(), th_draw)[0]       # (the streams from their start: the same numbers, in one call)
+            else:
+                for i, s in enumerate(sims):
+                    gen = torch.Generator(device=self.device)
+                    gen.manual_seed(self._stream(SimRng(seed, s)))
+                    xg.append(self._sample(gen, th_draw[i])[0].to(self.dtype))
+                Xg = torch.stack(xg)
             zfix = zhat.view((S,) + zshape)
             # H1[s, i, j] = ∂/∂θ_j of the score's component i through the draw: nθ backward passes, each over every simulation
             H1 = torch.zeros((S, nt, nt), dtype=self.dtype, device=self.device)
