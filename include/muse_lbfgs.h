@@ -48,6 +48,18 @@
  * is ignored.  A row whose p.Mp is not positive or not finite -- M is not positive definite there -- stops with y as it was and the
  * count -1 - iterations (include/muse_hip.h's convention for the implicit get_H!).
  *
+ * The same solver with a DIAGONAL (Jacobi) preconditioner Pl = Diagonal(d), in the order of IterativeSolvers' preconditioned cg: the
+ * number of rounds is the cost of a solve (every round is one application of the caller's operator, one launch and one
+ * synchronisation), and a preconditioner is the only lever on it.  muse_lbfgs_pcg_begin / muse_lbfgs_pcg_advance take the place of
+ * muse_lbfgs_cg_begin / muse_lbfgs_cg_advance in the loop above; the workspace (muse_lbfgs_cg_workspace_bytes: r / d is formed where it
+ * is used and never stored) and muse_lbfgs_cg_result are shared, and a workspace may be used for one kind of solve after the other.
+ * diag: [nrows / rows_per_diag][n] doubles in device memory, the caller's, the same from begin to the last advance; row r reads
+ * diagonal row r / rows_per_diag (get_H!: the columns of one simulation share one Hessian, so its diagonal is held once).  The first
+ * direction is b / d; the stopping rule is plain CG's, on |r|_2.  Any diagonal of positive finite entries gives the same solution to
+ * the tolerance -- only the count moves; a row whose diagonal holds an entry that is not positive or not finite is stopped in begin
+ * with y = 0 and the count -1 (its p_eval row is b), unless it needs no iteration at all (count 0, as in plain CG).  With d = 1 every
+ * value is plain CG's.
+ *
  * Every function returns 0, or a negative number: MUSE_LBFGS_BAD_ARGUMENT, or -(100 + the hipError_t of a failed launch).
  */
 #ifndef MUSE_LBFGS_H
@@ -85,7 +97,8 @@ int muse_lbfgs_workgroup_size(int64_t n);
 
 /* ---- lock-step conjugate gradients (the shape limits and the workgroup size are those above) ---- */
 
-/* the workspace's size in bytes: one record per row and [nrows][2][n] doubles, y and r (negative: a bad argument) */
+/* the workspace's size in bytes: one record per row and [nrows][2][n] doubles, y and r (negative: a bad argument); the same for the
+ * preconditioned solver */
 int64_t muse_lbfgs_cg_workspace_bytes(int64_t nrows, int64_t n);
 
 /* start nrows systems with right-hand sides b: y = 0, r = b, the first direction (b itself) into p_eval, the tolerance
@@ -101,6 +114,16 @@ int muse_lbfgs_cg_advance(void* ws, int64_t nrows, int64_t n, const double* Mp, 
 /* the solutions y_out [nrows][n], the counts iterations_out [nrows] (int32; negative: -1 - iterations, the guard stopped the row) and
  * resnorm_out [nrows], the recurrence residual |r|_2 (all device memory) */
 int muse_lbfgs_cg_result(void* ws, int64_t nrows, int64_t n, double* y_out, int32_t* iterations_out, double* resnorm_out, void* stream);
+
+/* muse_lbfgs_cg_begin with the preconditioner Diagonal(diag): y = 0, r = b, the first direction b / d into p_eval.  diag is
+ * [nrows / rows_per_diag][n]; a bad argument also: a null diag, rows_per_diag < 1, nrows not a multiple of rows_per_diag.  A row whose
+ * diagonal holds an entry that is not positive or not finite is finished with the count -1 and b in its p_eval row */
+int muse_lbfgs_pcg_begin(void* ws, int64_t nrows, int64_t n, const double* b, const double* diag, int64_t rows_per_diag, double reltol,
+                         double abstol, int maxiter, double* p_eval, int* active_out, void* stream);
+
+/* muse_lbfgs_cg_advance for a solve begun by muse_lbfgs_pcg_begin, with the same diag and rows_per_diag */
+int muse_lbfgs_pcg_advance(void* ws, int64_t nrows, int64_t n, const double* Mp, const double* diag, int64_t rows_per_diag, double* p_eval,
+                           int* active_out, void* stream);
 
 /* ---- the engine's normal stream, for all rows of a map in one launch ----
  *

@@ -161,6 +161,8 @@ LBFGS_SIGNATURES = {
     "muse_lbfgs_cg_begin": (_i, [_vp, _i64, _i64, _vp, _d, _d, _i, _vp, _vp, _vp]),
     "muse_lbfgs_cg_advance": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "muse_lbfgs_cg_result": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "muse_lbfgs_pcg_begin": (_i, [_vp, _i64, _i64, _vp, _vp, _i64, _d, _d, _i, _vp, _vp, _vp]),
+    "muse_lbfgs_pcg_advance": (_i, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
     # the engine's normal stream for all rows of a map: out, nrows, count, seed, sims, pair_offset, stream
     "muse_lbfgs_normals": (_i, [_vp, _i64, _i64, _u64, _vp, _i64, _vp]),
 }

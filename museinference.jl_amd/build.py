@@ -189,6 +189,7 @@ _LBFGS_API = os.path.join(INCLUDE_DIR, "muse_lbfgs.h")
 _LBFGS_SOURCE = os.path.join(LBFGS_DIR, "lbfgs_kernels.hip")
 _LBFGS_DEPS = [_LBFGS_SOURCE, os.path.join(LBFGS_DIR, "lbfgs_control.hpp"), os.path.join(LBFGS_DIR, "lbfgs_advance.hpp"),
                os.path.join(LBFGS_DIR, "cg_control.hpp"), os.path.join(LBFGS_DIR, "cg_advance.hpp"), os.path.join(LBFGS_DIR, "cg_kernels.hpp"),
+               os.path.join(LBFGS_DIR, "pcg_control.hpp"), os.path.join(LBFGS_DIR, "pcg_advance.hpp"), os.path.join(LBFGS_DIR, "pcg_kernels.hpp"),
                os.path.join(LBFGS_DIR, "normals_kernels.hpp"), _LBFGS_API, os.path.join(CSRC, "reduce.hpp"), os.path.join(CSRC, "args.hpp"),
                os.path.join(CSRC, "rng.hpp")]
 

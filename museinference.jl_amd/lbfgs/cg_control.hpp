@@ -19,10 +19,12 @@ namespace muse_lbfgs {
 
 // One row's state between two rounds: r.r, the tolerance, the count.  `count` is the number of iterations taken, or -1 - iterations
 // once the guard has stopped the row (p . M p not positive or not finite: M is not positive definite -- the convention of
-// include/muse_hip.h's implicit get_H!, which muse.py reads).
+// include/muse_hip.h's implicit get_H!, which muse.py reads).  `rho` is the preconditioned solver's (r / d) . r (pcg_control.hpp), which
+// shares the record, the workspace and the count and result kernels; plain CG keeps it at zero and never reads it.
 struct CgRecord {
     double rr, tol;
     int32_t count, maxiter, done, pad_;
+    double rho;
 };
 
 CG_HD bool cg_is_inf(double v) { return __builtin_fabs(v) == __builtin_inf(); }
@@ -40,6 +42,7 @@ CG_HD bool cg_init(CgRecord& c, double rr, double reltol, double abstol, int max
     c.count = 0;
     c.maxiter = maxiter;
     c.pad_ = 0;
+    c.rho = 0.0;
     c.done = (maxiter <= 0 || cg_converged(c)) ? 1 : 0;
     return !c.done;
 }

@@ -22,6 +22,7 @@ __device__ __forceinline__ void load_cg_record(CgRecord& d, const CgRecord& s) {
     d.maxiter = uniform_i(s.maxiter);
     d.done = uniform_i(s.done);
     d.pad_ = 0;
+    d.rho = 0.0;
 }
 
 template <int T>

@@ -342,5 +342,8 @@ int muse_lbfgs_workgroup_size(int64_t n) { return n <= kSmallMaxN ? kSmallT : kL
 // muse_lbfgs_cg_*: the lock-step conjugate gradients, kernels and entry points (the same workgroup sizes, shape limits and helpers)
 #include "cg_kernels.hpp"
 
+// muse_lbfgs_pcg_*: the same solver with a diagonal preconditioner (the record, the workspace, the count and result kernels are shared)
+#include "pcg_kernels.hpp"
+
 // muse_lbfgs_normals: the engine's normal stream for all rows of a map in one launch (the batched closure problems' draws)
 #include "normals_kernels.hpp"

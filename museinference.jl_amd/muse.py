@@ -435,8 +435,8 @@ def _fd_batched(prob, rng, nsims, theta0, m, step, atol, fid_mode):
 def _cg_keywords(cg_kwargs):
     """implicit_diff_cg_kwargs (splatted into IterativeSolvers.cg by the reference, src/muse.jl:381) as the keywords of the
     implicit_H_batch seam: maxiter, reltol, abstol; Pl as the identity (None or an identity matrix) or the string "jacobi" -- the
-    diagonal of the Hessian the branch applies, formed by the kernel itself (the reference's users pass Diagonal(...) of it, which a
-    closure cannot carry across the C ABI): cg_Pl="jacobi" at the seam, only when given.  Any other key or Pl is an error, never
+    diagonal of the Hessian the branch applies, formed by the problem -- a header model's in the kernel itself, a closure problem's from
+    its hess_diag, given or probed (the reference's users pass Diagonal(...) of it, which a closure cannot carry across the C ABI): cg_Pl="jacobi" at the seam, only when given.  Any other key or Pl is an error, never
     ignored."""
     kw = dict(cg_kwargs or {})
     out = {"cg_maxiter": int(kw.pop("maxiter", 100))}
@@ -449,7 +449,7 @@ def _cg_keywords(cg_kwargs):
         if isinstance(Pl, str):
             if Pl != "jacobi":
                 raise ValueError(f'implicit_diff_cg_kwargs: Pl must be the identity (None or an identity matrix) or "jacobi" (the '
-                                 f"Hessian's diagonal, formed in the kernel); got {Pl!r}")
+                                 f"Hessian's diagonal, formed by the problem); got {Pl!r}")
             out["cg_Pl"] = "jacobi"
         elif Pl is not None:
             try:
@@ -458,7 +458,7 @@ def _cg_keywords(cg_kwargs):
                 P = None
             if P is None or P.ndim != 2 or P.shape[0] != P.shape[1] or not np.array_equal(P, np.eye(P.shape[0])):
                 raise ValueError('implicit_diff_cg_kwargs: Pl must be the identity (None or an identity matrix) or "jacobi" (the '
-                                 "Hessian's diagonal, formed in the kernel): a matrix or a closure of the caller's does not cross the "
+                                 "Hessian's diagonal, formed by the problem): a matrix or a closure of the caller's does not cross the "
                                  "C ABI")
     if kw:
         raise ValueError(f"implicit_diff_cg_kwargs: unsupported key(s) {sorted(kw)} (supported: maxiter, reltol, abstol, "

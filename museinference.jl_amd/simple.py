@@ -23,13 +23,65 @@ from . import optim
 
 
 class TorchMuseProblem(AbstractMuseProblem):
-    def __init__(self, x, sample_x_z, logLike, logPrior=None, device=None, dtype=None):
+    def __init__(self, x, sample_x_z, logLike, logPrior=None, device=None, dtype=None, hess_diag=None):
         import torch
         self._torch = torch
         self.device = torch.device(device) if device is not None else (x.device if torch.is_tensor(x) else torch.device("cpu"))
         self.dtype = dtype or torch.float64
         self.x = None if x is None else self._t(x)
         self._sample, self._logLike, self._logPrior = sample_x_z, logLike, logPrior
+        self._hess_diag = self._checked_hess_diag(hess_diag)
+
+    # -- what implicit_diff_cg_kwargs' Pl = "jacobi" means for a closure: the diagonal of -∂²logLike/∂z² at a fiducial MAP
+    def _checked_hess_diag(self, hess_diag):
+        """hess_diag: None; a callable (x [B, ...], z [B, ...], θ [B, nθ]) -> [B, ...], the diagonal itself; "elementwise" (one all-ones
+        probe: exact for uncoupled latents); or a tensor of probes [k, *zshape] with 0 / 1 entries that partition the latent elements --
+        the diagonal is then Σ_c v_c ⊙ (M v_c), k Hessian-vector products, exact when no two coupled elements share a probe (a
+        colouring, for stencil-like couplings).  The diagonal only preconditions conjugate gradients: any positive one gives the same
+        H to the tolerance and only the counts move, so an inexact probing costs iterations, never correctness; a diagonal that is
+        not positive is reported through a negative count."""
+        torch = self._torch
+        if hess_diag is None or callable(hess_diag) or (isinstance(hess_diag, str) and hess_diag == "elementwise"):
+            return hess_diag
+        if isinstance(hess_diag, str) or not torch.is_tensor(hess_diag):
+            raise ValueError(f'hess_diag must be None, a callable, "elementwise" or a tensor of probes [k, *zshape]; got {hess_diag!r}')
+        probes = hess_diag.detach().to(self.device, self.dtype)
+        if probes.dim() < 2 or probes.shape[0] < 1:
+            raise ValueError("hess_diag: a tensor of probes has shape [k, *zshape] with k >= 1")
+        if not bool(((probes == 0) | (probes == 1)).all()) or not bool((probes.sum(dim=0) == 1).all()):
+            raise ValueError("hess_diag: the probes must partition the latent elements (entries 0 or 1, every element in exactly one probe)")
+        return probes
+
+    @staticmethod
+    def _checked_cg_Pl(cg_Pl, hess_diag):
+        if cg_Pl is None:
+            return False
+        if not (isinstance(cg_Pl, str) and cg_Pl == "jacobi"):
+            raise ValueError(f'implicit_H_batch: cg_Pl must be None (the identity) or "jacobi"; got {cg_Pl!r}')
+        if hess_diag is None:
+            raise ValueError('implicit_H_batch: cg_Pl="jacobi" needs the diagonal of the closure\'s Hessian in z: construct the problem with '
+                             'hess_diag (a callable, a tensor of probes or "elementwise")')
+        return True
+
+    def _hess_diagonal(self, X, Z, TH, hvp):
+        """The diagonal [S, N] of M = -∂²logLike/∂z² for S simulations at Z [S, *zshape]; hvp(V [S, *zshape]) -> M V [S, *zshape]."""
+        torch = self._torch
+        S, zshape = Z.shape[0], tuple(Z.shape[1:])
+        hd = self._hess_diag
+        if callable(hd):
+            with torch.no_grad():
+                d = hd(X, Z, TH)
+            if not torch.is_tensor(d) or d.numel() != Z.numel():
+                raise ValueError(f"hess_diag(x, z, θ) must return a tensor of z's shape {tuple(Z.shape)}")
+            return d.detach().to(self.device, self.dtype).reshape(S, -1).contiguous()
+        probes = torch.ones((1,) + zshape, dtype=self.dtype, device=self.device) if isinstance(hd, str) else hd
+        if tuple(probes.shape[1:]) != zshape:
+            raise ValueError(f"hess_diag: probes of shape {tuple(probes.shape)} do not match the latent shape {zshape}")
+        d = torch.zeros((S,) + zshape, dtype=self.dtype, device=self.device)
+        for c in range(probes.shape[0]):
+            V = probes[c].expand((S,) + zshape).contiguous()
+            d = d + V * hvp(V).detach().reshape(V.shape)
+        return d.reshape(S, -1).contiguous()
 
     # -- tensors in, numpy for theta-sized results out (the driver's algebra is numpy)
     def _t(self, v):
@@ -101,13 +153,16 @@ class TorchMuseProblem(AbstractMuseProblem):
         return self._torch.zeros_like(self._t(z))
 
     # -- get_H! by implicit differentiation (src/muse.jl:335-405), every derivative by autograd as the reference takes them by nested AD
-    def implicit_H_batch(self, seed, sim_begin, sim_end, theta0, atol=1e-1, cg_maxiter=100, cg_reltol=1.4901161193847656e-08):
+    def implicit_H_batch(self, seed, sim_begin, sim_end, theta0, atol=1e-1, cg_maxiter=100, cg_reltol=1.4901161193847656e-08, cg_Pl=None):
         """Per simulation H = H1 - dFdθᵀ A⁻¹ dFdθ1: H1 the Jacobian of the score through the DRAW x(θ) at fixed ẑ, dFdθ = ∂θ ∇z logLike,
         dFdθ1 = ∂θ ∇z logLike(x(θ), ẑ, θ₀), A the Hessian of logLike in z applied by double backward, A⁻¹ by conjugate gradients (reltol
         sqrt(eps), maxiter 100: IterativeSolvers' defaults).  The draw is differentiated through the closure itself (the generator
         re-seeded: the same random numbers at every θ), so sample_x_z must be written with differentiable torch operations.
-        Returns (Hs [n, nθ, nθ], CG iteration counts [n, nθ])."""
+        cg_Pl="jacobi" preconditions the solves with the diagonal the constructor's hess_diag describes (_pcg; a ValueError, raised before
+        any draw, without one): the same H to the tolerance, fewer iterations; a count is then -1 - iterations where the diagonal or
+        p.Ap was not positive.  Returns (Hs [n, nθ, nθ], CG iteration counts [n, nθ])."""
         torch = self._torch
+        jacobi = self._checked_cg_Pl(cg_Pl, self._hess_diag)
         th0 = self._theta(theta0)
         nt = th0.numel()
         Hs, its = [], []
@@ -139,9 +194,14 @@ class TorchMuseProblem(AbstractMuseProblem):
 
                 def A(w):          # Hessian of logLike in z at the MAP, applied
                     return torch.autograd.grad(g, zz, w.reshape(zz.shape), retain_graph=True)[0].reshape(-1)
+                if jacobi:
+                    d = self._hess_diagonal(x[None], zh[None], th0[None], lambda V: -A(V[0])[None])[0]
                 cols, n_it = [], []
                 for j in range(nt):
-                    y, k = _cg(lambda w: -A(w), -dF1[:, j].detach(), cg_maxiter, cg_reltol)     # (-A is positive definite at a maximum)
+                    if jacobi:
+                        y, k = _pcg(lambda w: -A(w), -dF1[:, j].detach(), d, cg_maxiter, cg_reltol)
+                    else:
+                        y, k = _cg(lambda w: -A(w), -dF1[:, j].detach(), cg_maxiter, cg_reltol)     # (-A is positive definite at a maximum)
                     cols.append(y)
                     n_it.append(k)
             H = H1.detach() - dF.detach().T @ torch.stack(cols, dim=1)
@@ -210,6 +270,7 @@ class LbfgsBatch:
         self._active = torch.zeros(1, dtype=torch.int32).pin_memory()
         self._info = torch.empty(self.nprob * _capi.INFO_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
         self.rounds = self.syncs = 0
+        self._diag = None          # (diagonal, rows_per_diag) of a preconditioned solve, from begin to result
         self.timing, self.advance_ms = False, 0.0      # timing: device time of the advance launches, summed (tools/closures_bench.py)
 
     def _stream(self):
@@ -265,7 +326,8 @@ class CgBatch:
 
         active = cg.begin(b, reltol, abstol, maxiter);  while active: Mp = M applied to cg.p_eval -> active = cg.advance(Mp);  cg.result()
 
-    The direction lives in `p_eval` and nowhere else: read it, never write it.
+    The direction lives in `p_eval` and nowhere else: read it, never write it.  begin(..., diag=d) preconditions the solve with
+    Diagonal(d) (see there); without it every call is plain CG's.
     """
 
     def __init__(self, device, nrows, n):
@@ -283,6 +345,7 @@ class CgBatch:
         self._its = torch.empty(self.nrows, dtype=torch.int32, device=self.device)
         self._res = torch.empty(self.nrows, dtype=torch.float64, device=self.device)
         self.rounds = self.syncs = 0
+        self._diag = None          # (diagonal, rows_per_diag) of a preconditioned solve, from begin to result
         self.timing, self.advance_ms = False, 0.0      # timing: device time of the advance launches, summed (tools/closures_implicit_bench.py)
 
     def _stream(self):
@@ -301,14 +364,35 @@ class CgBatch:
         self.syncs += 1
         return int(self._active[0])
 
-    def begin(self, b, reltol, abstol=0.0, maxiter=100):
-        """Start every row at y = 0 with right-hand side b [nrows, n]; p_eval = b.  Returns the number of active rows (one synchronisation)."""
+    def _diagonal(self, diag, rows_per_diag):
+        torch, k = self._torch, int(rows_per_diag)
+        if k < 1 or self.nrows % k != 0:
+            raise ValueError(f"rows_per_diag must be at least 1 and divide the number of rows ({self.nrows}); got {rows_per_diag!r}")
+        shape = (self.nrows // k, self.n)
+        if not (torch.is_tensor(diag) and diag.device == self.p_eval.device and diag.dtype == torch.float64 and tuple(diag.shape) == shape):
+            raise ValueError(f"diag: expected a float64 tensor of shape {shape} on {self.p_eval.device}")
+        return diag.contiguous(), k
+
+    def begin(self, b, reltol, abstol=0.0, maxiter=100, diag=None, rows_per_diag=1):
+        """Start every row at y = 0 with right-hand side b [nrows, n]; p_eval = b.  Returns the number of active rows (one synchronisation).
+
+        With `diag` -- a float64 tensor [nrows / rows_per_diag, n] on the device, row r reading diagonal row r // rows_per_diag -- the
+        solve is preconditioned by Diagonal(diag) (muse_lbfgs_pcg_*): p_eval = b / diag, and advance() goes on with the same diagonal,
+        which is held until result().  Any diagonal of positive finite entries gives the same solution to the tolerance, only the
+        counts move; a row whose diagonal holds an entry that is not positive or not finite ends at once with the count -1 and y = 0."""
         b = self._rows(b)
+        self._diag = None if diag is None else self._diagonal(diag, rows_per_diag)
         self.rounds = self.syncs = 0
         self.advance_ms = 0.0
         with self._torch.cuda.device(self.device):
-            self._capi.check_lbfgs(self._lib.muse_lbfgs_cg_begin(self._ws.data_ptr(), self.nrows, self.n, b.data_ptr(), float(reltol), float(abstol),
-                                                                 int(maxiter), self.p_eval.data_ptr(), self._active.data_ptr(), self._stream()))
+            if self._diag is None:
+                rc = self._lib.muse_lbfgs_cg_begin(self._ws.data_ptr(), self.nrows, self.n, b.data_ptr(), float(reltol), float(abstol),
+                                                   int(maxiter), self.p_eval.data_ptr(), self._active.data_ptr(), self._stream())
+            else:
+                d, k = self._diag
+                rc = self._lib.muse_lbfgs_pcg_begin(self._ws.data_ptr(), self.nrows, self.n, b.data_ptr(), d.data_ptr(), k, float(reltol),
+                                                    float(abstol), int(maxiter), self.p_eval.data_ptr(), self._active.data_ptr(), self._stream())
+            self._capi.check_lbfgs(rc)
         return self._wait()
 
     def advance(self, Mp):
@@ -319,8 +403,14 @@ class CgBatch:
             e0, e1 = self._torch.cuda.Event(enable_timing=True), self._torch.cuda.Event(enable_timing=True)
             e0.record(stream)
         with self._torch.cuda.device(self.device):
-            self._capi.check_lbfgs(self._lib.muse_lbfgs_cg_advance(self._ws.data_ptr(), self.nrows, self.n, Mp.data_ptr(), self.p_eval.data_ptr(),
-                                                                   self._active.data_ptr(), self._stream()))
+            if self._diag is None:
+                rc = self._lib.muse_lbfgs_cg_advance(self._ws.data_ptr(), self.nrows, self.n, Mp.data_ptr(), self.p_eval.data_ptr(),
+                                                     self._active.data_ptr(), self._stream())
+            else:
+                d, k = self._diag
+                rc = self._lib.muse_lbfgs_pcg_advance(self._ws.data_ptr(), self.nrows, self.n, Mp.data_ptr(), d.data_ptr(), k,
+                                                      self.p_eval.data_ptr(), self._active.data_ptr(), self._stream())
+            self._capi.check_lbfgs(rc)
         if self.timing:
             e1.record(stream)
         active = self._wait()
@@ -338,6 +428,7 @@ class CgBatch:
                                                                   self._res.data_ptr(), self._stream()))
         its, res = self._its.cpu().numpy().copy(), self._res.cpu().numpy().copy()
         self.syncs += 1
+        self._diag = None
         return y, its, res
 
 
@@ -413,10 +504,11 @@ class BatchedTorchMuseProblem(TorchMuseProblem):
     MAX_ROUNDS = 200000
     IMPLICIT_MAX_ELEMS = 1 << 24     # implicit_H_batch: simulations per chunk so that (rows = nsims nθ) x N stays at or below this
 
-    def __init__(self, x, sample_x_z, logLike, logPrior=None, device=None, dtype=None, logLike_batched=None, sample_x_z_batched=None):
+    def __init__(self, x, sample_x_z, logLike, logPrior=None, device=None, dtype=None, logLike_batched=None, sample_x_z_batched=None,
+                 hess_diag=None):
         if sample_x_z is None and sample_x_z_batched is None:
             raise ValueError("BatchedTorchMuseProblem needs sample_x_z or sample_x_z_batched")
-        super().__init__(x, sample_x_z, logLike, logPrior, device, dtype)
+        super().__init__(x, sample_x_z, logLike, logPrior, device, dtype, hess_diag=hess_diag)
         from . import _capi
         if self.device.type != "cuda":
             raise _capi.MuseError(-3, "no HIP device available (BatchedTorchMuseProblem runs libmuse_lbfgs's kernels: there is no CPU fallback)")
@@ -632,14 +724,25 @@ class BatchedTorchMuseProblem(TorchMuseProblem):
 
     # -- get_H! by implicit differentiation, all simulations at once
     def implicit_H_batch(self, seed, sim_begin, sim_end, theta0, atol=1e-1, cg_maxiter=100, cg_reltol=1.4901161193847656e-08, cg_abstol=0.0,
-                         H1_is_zero=False):
+                         H1_is_zero=False, cg_Pl=None):
         """The serial class's implicit_H_batch (H = H1 - dFdθᵀ A⁻¹ dFdθ1 per simulation, see there) with every step taken for all
         simulations at once: the fiducial MAPs are one lock-step L-BFGS batch, the derivative terms one autograd pass per θ component
         over the whole batch, and the nsims nθ linear solves one lock-step conjugate-gradient batch of libmuse_lbfgs.so (CgBatch: one
         workgroup per (simulation, column), the operator one double backward of the batched closure per round, one word read per round).
         cg_abstol and H1_is_zero are IterativeSolvers' abstol and the reference's implicit_diff_H1_is_zero.  Simulations are taken in
-        chunks of at most IMPLICIT_MAX_ELEMS / (nθ N); rows are independent.  Returns (Hs [n, nθ, nθ], CG counts [n, nθ]: negative,
-        -1 - iterations, where p.Ap was not positive -- the Hessian in z is not negative definite at that fiducial MAP)."""
+        chunks of at most IMPLICIT_MAX_ELEMS / (nθ N); rows are independent.
+
+        cg_Pl="jacobi" (implicit_diff_cg_kwargs' Pl) preconditions every solve with the diagonal of -∂²logLike/∂z² at its simulation's
+        fiducial MAP, as the constructor's hess_diag describes it (given by a callable, or probed by Hessian-vector products over the
+        simulations): one [nsims, N] diagonal shared by a simulation's nθ rows, applied inside the CG kernel.  Every round is a double
+        backward pass, a launch and a synchronisation, so the number of rounds is the cost of the call and the diagonal the lever on
+        it.  Correctness never rests on the diagonal's quality: any positive one gives the same H to the tolerance and only the counts
+        move; one that is not positive (or not finite) gives that simulation's rows the count -1.  Without hess_diag "jacobi" is a
+        ValueError, raised before any draw or launch; a general (non-diagonal) preconditioner is not supported.
+
+        Returns (Hs [n, nθ, nθ], CG counts [n, nθ]: negative, -1 - iterations, where p.Ap was not positive -- the Hessian in z is not
+        negative definite at that fiducial MAP -- or the diagonal was not usable)."""
+        jacobi = self._checked_cg_Pl(cg_Pl, self._hess_diag)
         seed = int(seed.seed) if isinstance(seed, SimRng) else int(seed)
         theta0 = np.atleast_1d(np.asarray(theta0, dtype=np.float64))
         sims = list(range(int(sim_begin), int(sim_end)))
@@ -650,7 +753,7 @@ class BatchedTorchMuseProblem(TorchMuseProblem):
         self.last_cg_advance_ms = 0.0
         Hs, its, infos = [], [], []
         for c in range(0, len(sims), per):
-            H, k, info = self._implicit_chunk(seed, sims[c:c + per], theta0, atol, cg_maxiter, cg_reltol, cg_abstol, H1_is_zero)
+            H, k, info = self._implicit_chunk(seed, sims[c:c + per], theta0, atol, cg_maxiter, cg_reltol, cg_abstol, H1_is_zero, jacobi)
             Hs.append(H)
             its.append(k)
             infos.append(info)
@@ -659,7 +762,7 @@ class BatchedTorchMuseProblem(TorchMuseProblem):
             return np.zeros((0, nt, nt)), np.zeros((0, nt), dtype=np.int32)
         return np.concatenate(Hs), np.concatenate(its)
 
-    def _implicit_chunk(self, seed, sims, theta0, atol, cg_maxiter, cg_reltol, cg_abstol, H1_is_zero):
+    def _implicit_chunk(self, seed, sims, theta0, atol, cg_maxiter, cg_reltol, cg_abstol, H1_is_zero, jacobi=False):
         torch = self._torch
         S, nt = len(sims), theta0.size
         TH = self._theta_rows(theta0, S)
@@ -720,7 +823,15 @@ class BatchedTorchMuseProblem(TorchMuseProblem):
                 self._cg_batch = CgBatch(self.device, R, N)
             cg = self._cg_batch
             cg.timing = self.cg_timing
-            active = cg.begin(b.reshape(R, N), cg_reltol, cg_abstol, cg_maxiter)
+            if jacobi:
+                # the diagonal at the S fiducial MAPs, [S, N]: row (s, j) of the batch reads diagonal row s
+                ZS = zfix.clone().requires_grad_(True)
+                gS, = torch.autograd.grad(self._logLike_rows(X, ZS, TH).sum(), ZS, create_graph=True)
+                diag = self._hess_diagonal(X, zfix, TH, lambda V: -torch.autograd.grad(gS, ZS, V, retain_graph=True)[0])
+                del gS, ZS
+                active = cg.begin(b.reshape(R, N), cg_reltol, cg_abstol, cg_maxiter, diag=diag, rows_per_diag=nt)
+            else:
+                active = cg.begin(b.reshape(R, N), cg_reltol, cg_abstol, cg_maxiter)
             while active > 0:
                 Ap, = torch.autograd.grad(g, ZR, cg.p_eval.view_as(g), retain_graph=True)
                 active = cg.advance(-Ap.reshape(R, N))
@@ -762,6 +873,40 @@ def _cg(A, b, maxiter, reltol):
         rs = rs_new
         k += 1
     return y, k
+
+
+def _pcg(A, b, d, maxiter, reltol, abstol=0.0):
+    """Conjugate gradients for A y = b from y = 0 preconditioned by Diagonal(d) (IterativeSolvers' cg with Pl; the serial statement of
+    lbfgs/pcg_control.hpp, decision for decision): (y, count).  Stops at |r| <= max(reltol |b|, abstol) or after maxiter iterations; the
+    count is -1 - iterations where the guard stopped the solve with y as it was -- p.Ap not positive or not finite, or (before the
+    first iteration) an entry of d that is not positive or not finite.  Any positive d gives the same solution to the tolerance."""
+    import math
+    y = b.new_zeros(b.shape)
+    r = b.clone()
+    rr = float(r.dot(r))
+    tol = max(reltol * math.sqrt(rr), abstol)
+    if maxiter <= 0 or math.sqrt(rr) <= tol:
+        return y, 0
+    if not bool(((d > 0) & ~d.isinf()).all()):
+        return y, -1
+    p = r / d
+    rho = float(p.dot(r))
+    k = 0
+    while True:
+        Ap = A(p)
+        pAp = float(p.dot(Ap))
+        if not (pAp > 0.0) or math.isinf(pAp):
+            return y, -1 - k
+        alpha = rho / pAp
+        y = y + alpha * p
+        r = r - alpha * Ap
+        c = r / d
+        rr, rho_new = float(r.dot(r)), float(c.dot(r))
+        k += 1
+        if k == maxiter or math.sqrt(rr) <= tol:
+            return y, k
+        p = c + (rho_new / rho) * p
+        rho = rho_new
 
 
 def _fd_grad(f, t, step=1e-6):
