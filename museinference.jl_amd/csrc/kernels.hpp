@@ -492,13 +492,15 @@ muse_loop_kernel(const BatchArgs /*read via the kernarg segment*/, const LoopArg
                     iteration_setup(iter + 1);
                 }
 #else
+                double zero = 0.0;
+                asm volatile("" : "+s"(zero));   // (else the dead components' 64-bit zero is formed at the kernel's entry and held -- in scratch -- across the solves)
                 if (tl < kMaxTheta) {
                     const bool live = tl < nt;
-                    a.cur.t.theta[tl] = live ? th[tl] : 0.0;
-                    a.cur.t.sd[tl] = live ? muse_exp(0.5 * th[tl]) : 0.0;
+                    a.cur.t.theta[tl] = live ? th[tl] : zero;
+                    a.cur.t.sd[tl] = live ? muse_exp(0.5 * th[tl]) : zero;
                 } else if (tl < 2 * kMaxTheta) {
                     const int k = tl - kMaxTheta;
-                    a.cur.t.iv[k] = k < nt ? muse_exp(-th[k]) : 0.0;
+                    a.cur.t.iv[k] = k < nt ? muse_exp(-th[k]) : zero;
                 } else if (tl == 2 * kMaxTheta) {
                     make_map_theta_const(nt, a.bnd, th, a.cur);
                 } else if (tl == 2 * kMaxTheta + 1) {
@@ -556,7 +558,7 @@ muse_loop_kernel(const BatchArgs /*read via the kernarg segment*/, const LoopArg
             StepWork& w = *reinterpret_cast<StepWork*>(small + 24);
             if (tid == 0) {
                 int zero = 0;
-                asm volatile("" : "+v"(zero));   // (else a 64-bit zero is held across the stepper's own solves, in scratch)
+                asm volatile("" : "+s"(zero));   // (else a 64-bit zero is held across the stepper's own solves, in scratch)
                 a.gran_tag = L.tag_base + (unsigned)iter;
                 m.flags[0] = zero;
                 m.flags[1] = zero;

@@ -75,7 +75,14 @@ template <>
 struct PairState<true> {
     double pc[4], psd[2];
 };
+// UNIFORM_LS: the line search's constants are laundered through SGPRs (wolfe()), so that the HagerZhang machine's control flow is
+// scalar.  The LDS-resident placement with several components sits at the register file's limit, and there the machine's state in
+// SGPRs -- spilled to VGPR lanes around the evaluation site -- pushed vector registers into scratch (single-instantiation builds:
+// FunnelModel<4> map kernel 0 -> 5 spilled VGPRs, its loop kernel 29 -> 45, FunnelModel<8> 8 -> 15): those entry points keep the
+// VGPR launder, the code they always had.
 template <class Model, class Place>
+constexpr bool uniform_linesearch() { return !(Place::kResident && Place::kXgLds && Model::MAXB > 1); }
+template <class Model, class Place, bool UNIFORM_LS = uniform_linesearch<Model, Place>()>
 struct Solver : PairState<Model::kPair> {
     static constexpr int T = Place::T, EPT = Place::EPT, U = Place::U, MAXB = Model::MAXB;
     // The big tier (kMaxTheta < ntheta <= kBigTheta, streaming placements only): the per-block coefficients come from the
@@ -911,8 +918,12 @@ struct Solver : PairState<Model::kPair> {
                                                  double phi_lim) {
         // the constants are materialised here (two moves each): hoisted to the kernel's entry they stay live across
         // the persistent loop and, in the register-bound placements, come back from scratch in every line search
+        // (laundered through SGPRs: the output of an inline-asm statement that is constrained to a VGPR counts as DIVERGENT,
+        //  and with it the Wolfe test and everything control-dependent on it -- the machine's state, cont, iter, the point ids,
+        //  the loop's exit -- which then lived in VGPRs behind exec masks)
         double delta = kHzDelta, sigma = kHzSigma, delta2 = 2.0 * kHzDelta - 1.0;
-        if constexpr (Place::kResident) asm volatile("" : "+v"(delta), "+v"(sigma), "+v"(delta2));
+        if constexpr (Place::kResident && UNIFORM_LS) asm volatile("" : "+s"(delta), "+s"(sigma), "+s"(delta2));
+        else if constexpr (Place::kResident) asm volatile("" : "+v"(delta), "+v"(sigma), "+v"(delta2));
         const bool w1 = (delta * dphi_0 >= (phi_c - phi_0) / c) && (dphi_c >= sigma * dphi_0);
         const bool w2 = (delta2 * dphi_0 >= dphi_c) && (dphi_c >= sigma * dphi_0) && (phi_c <= phi_lim);
         return w1 || w2;
@@ -942,8 +953,18 @@ struct Solver : PairState<Model::kPair> {
         if (dphi_0 >= 0.0 || c0 <= kEps) return true;    // alpha = 0, nothing evaluated
         const double phi_lim = phi_0 + kHzEpsilon * fabs(phi_0);
         const HzPoint P0{0.0, phi_0, dphi_0, 0};
-        HzPoint A = P0, B = P0, C = P0, prev = P0, a0 = P0, b0 = P0;
-        double alphamax = INFINITY, cold = 0.0, fail_alpha = 0.0, c = c0;
+        HzPoint A = P0, B = P0, C = P0, a0 = P0, b0 = P0;
+        // prev: the look-back point of the bracketing phase -- the latest trial with phi <= phi_lim and dphi < 0, P0 at first --
+        // and cold, its step, which the expansion grows from.  Resident placements: both ARE A (nothing reads A as an endpoint
+        // before a bracket exists, and whichever way the bracketing ends it sets A = prev or A = P0): with the machine's state in
+        // scalar registers, copies of their own were nine more of them live across the evaluation site, spilled to VGPR lanes
+        // there.  The streaming placements keep the copies, i.e. the code they had (noise_1e6 measured 1 % slower without them:
+        // another schedule of the passes that carry the background generator).
+        HzPoint prev_own = P0;
+        double cold_own = 0.0;
+        HzPoint& prev = Place::kResident ? A : prev_own;
+        double& cold = Place::kResident ? A.a : cold_own;
+        double alphamax = INFINITY, fail_alpha = 0.0, c = c0;
         int state = S_INIT, cont = CONT_BRACKET, iter = 1, iterfinite = 1, nid = 1;
         bool ok = true;
         for (;;) {

@@ -193,7 +193,7 @@ MUSE_HD void step_component(const StepParams& sp, int k, const double* theta, co
     } else {
         double zero = 0.0;
 #if defined(__HIP_DEVICE_COMPILE__)
-        asm volatile("" : "+v"(zero));   // (the loop kernel: else the 64-bit zero is formed before the stepper's loop and held -- in scratch --
+        asm volatile("" : "+s"(zero));   // (the loop kernel: else the 64-bit zero is formed before the stepper's loop and held -- in scratch --
                                          //  across the stepper's own solves; the same bits either way)
 #endif
         w.gprior[k] = zero;

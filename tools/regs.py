@@ -81,7 +81,31 @@ def compile_one(inst, out, loop=False):
                           cwd=CSRC, stderr=subprocess.DEVNULL)
 
 
+def exec_masks(path, kernel="map_score"):
+    """How many s_and_saveexec_b64 -- branches taken by masking lanes off instead of jumping -- the `kernel` of an assembly
+    file holds.  The solver's control flow is workgroup-uniform: what is left after scalar branches are the lane-dependent
+    conditions (lane 0 of a wave, thread 0, the validity mask, the poll of a flag) -- DESIGN.md §1, the inline-asm rule."""
+    txt = open(path).read()
+    m = re.search(r"^_ZN4muse\d+%s_kernel\S*:[^\n]*\n(.*?)\n\s*s_endpgm" % kernel, txt, re.S | re.M)
+    if not m:
+        raise RuntimeError(f"{path}: no {kernel} kernel")
+    return m.group(1).count("s_and_saveexec_b64")
+
+
+def _sources_stamp():
+    return tuple(sorted((f, os.path.getmtime(os.path.join(CSRC, f))) for f in os.listdir(CSRC)))
+
+
 def check():
+    """(One set of compilations per process and state of the sources: the suite asks twice, and the answer takes minutes.)"""
+    cache = sys.modules.setdefault("_muse_regs_check_cache", type(sys)("_muse_regs_check_cache")).__dict__
+    key = ("check", _sources_stamp())
+    if key not in cache:
+        cache[key] = _check()
+    return list(cache[key])
+
+
+def _check():
     bad = []
     with tempfile.TemporaryDirectory() as d:
         for inst, limit in HOT:
