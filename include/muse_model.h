@@ -20,8 +20,9 @@
  * The score follows from the family:  d logLike / d theta_k = 1/2 (iv_k sum_{i in k} B(x_i, z_i) - n_k).
  *
  * The header defines (MUSE_MODEL_FN is supplied by the includer: host + device, inlined; plain C, doubles only, every
- * operation an IEEE + - * / sqrt or fma() -- the engine and its CPU checker compile the SAME text without
- * floating-point contraction, which is what makes their results comparable bit for bit):
+ * operation an IEEE + - * / sqrt or fma(), or the contract's exponential muse_model_exp(x) -- see EXPONENTIALS below --; the
+ * engine and its CPU checker compile the SAME text without floating-point contraction, which is what makes their results
+ * comparable bit for bit):
  *
  *     #define MUSE_MODEL_NAME "cubic"
  *     MUSE_MODEL_FN void   muse_model_sample(double sd, double n1, double n2, double* z, double* x, long i);
@@ -135,6 +136,28 @@
  * museinference_jl_amd.ElementwiseModel.from_pair_expressions writes both functions from the model's terms; muse_model_eval_pair_second
  * of muse_hip.h evaluates them on the host, which is what check_model_consistency differentiates numerically.
  *
+ * EXPONENTIALS.  The per-element functions of the elementwise families may call  muse_model_exp(x)  -- and nothing else beyond
+ * + - * / sqrt fma: no log, no pow, no trigonometric function --:
+ *     one-parameter family:  muse_model_sample, muse_model_grad, muse_model_score_term, muse_model_second, muse_model_dx_dsd
+ *     two-parameter family:  muse_model_coefs (as before), muse_model_sample, muse_model_grad, muse_model_score_terms,
+ *                            muse_model_score, muse_model_pair_second, muse_model_pair_dx
+ * (a response header, MUSE_MODEL_RESPONSE below, may not).  What lets a latent enter through its exponential per element and per
+ * evaluation: x_i ~ N(0, e^z_i) (models/stochastic_volatility.h), x_i ~ N(2 (e^(z_i/2) - 1), 1) (models/lognormal_obs.h).  The macro
+ * is defined by whoever includes the header, and resolves to
+ *     on the host (muse_engine.cpp: the contract check, muse_model_eval, muse_model_coefs once per theta)   muse::muse_exp, csrc/step.hpp:
+ *         fdlibm's reduction and polynomial as one fixed sequence of IEEE operations, below 1 ulp;
+ *     in the CPU checker (oracle/muse_oracle.c)   mo_exp: that sequence restated;
+ *     in device code, in muse_model_coefs (the step of the loop kernel)   muse::muse_exp;
+ *     in device code, in every other function   muse::model_exp, csrc/model_math.hpp: the same reduction and polynomial as a
+ *         branch-free body -- the quotient by a refined reciprocal with one fused residual correction (the correctly rounded quotient,
+ *         as the IEEE division gives), the scaling by ldexp (one rounding, where the two-step product of muse_exp has one), the
+ *         special results selected at the end --
+ * and all four return THE SAME BITS for every double argument: NaN, +-inf, +-0, both cut-offs (above 709.78... +inf, below
+ * -745.13... +0) and subnormal results included (tests/test_gpu_model_exp.py compares the device's with the checker's over every
+ * exponent boundary).  A plain compile of the header by itself gets libm's exp (below).  One call costs about thirty double-precision
+ * operations: share it among the values of a function body (e^(z/2) is h' and, doubled, h), as the generator does
+ * (museinference_jl_amd.symbolic: `exp` in the terms of from_expressions / from_pair_expressions).
+ *
  * A RESPONSE BEHIND THE STENCIL OPERATOR (the coupled family).  The three families above are elementwise.  A header that says
  *     #define MUSE_MODEL_RESPONSE 1                    (before including this file)
  * states instead the pointwise response of the coupled stencil model (MUSE_MODEL_SMOOTH of muse_hip.h with run-time weights, noise
@@ -175,9 +198,9 @@
 #endif
 #endif
 #ifndef muse_model_exp
-/* The exponential a header of the two-parameter family forms its coefficients with.  The engine and its CPU checker define it
- * before they include the header -- one fixed sequence of IEEE operations, the same bits on host, device and checker; a plain
- * compile of the header by itself (a syntax check, an editor) gets libm's. */
+/* The exponential of a header's functions (EXPONENTIALS above).  The engine and its CPU checker define it before they include the
+ * header -- one fixed sequence of IEEE operations, the same bits on host, device and checker; a plain compile of the header by
+ * itself (a syntax check, an editor) gets libm's. */
 #include <math.h>
 #define muse_model_exp(x) exp(x)
 #endif

@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libmuse_hip.so")
 OBJ_DIR = os.path.join(_HERE, "build")
 _API = os.path.join(_HERE, "..", "include", "muse_hip.h")
-_KERNEL_HEADERS = [os.path.join(CSRC, h) for h in ("rng.hpp", "args.hpp", "vec.hpp", "reduce.hpp", "models.hpp", "user_model.hpp", "solver.hpp",
+_KERNEL_HEADERS = [os.path.join(CSRC, h) for h in ("rng.hpp", "args.hpp", "vec.hpp", "reduce.hpp", "models.hpp", "user_model.hpp", "model_math.hpp", "solver.hpp",
                                                     "step.hpp", "kernels.hpp")]
 _SWITCHES = os.path.join(CSRC, "switches.hpp")
 _HOST_LOOP = os.path.join(CSRC, "host_loop.h")      # host only: the muse! loop muse_run and muse_run_sharded share
@@ -34,7 +34,7 @@ UNITS = {
     **{f"kernels_part{n}": ("kernels_part.hip", _KERNEL_HEADERS + [_API], _DEVICE_FLAGS + [f"-DMUSE_PART={n}"]) for n in range(KERNEL_PARTS)},
     # host code: plain C++ against the HIP runtime API (no device pass)
     # (-ffp-contract=off here too: step.hpp's algebra must round on the host exactly as in the step kernel)
-    "muse_engine": ("muse_engine.cpp", [os.path.join(CSRC, "args.hpp"), os.path.join(CSRC, "step.hpp"), os.path.join(CSRC, "user_model.hpp"), _SWITCHES, _HOST_LOOP, _API],
+    "muse_engine": ("muse_engine.cpp", [os.path.join(CSRC, "args.hpp"), os.path.join(CSRC, "step.hpp"), os.path.join(CSRC, "user_model.hpp"), os.path.join(CSRC, "model_math.hpp"), _SWITCHES, _HOST_LOOP, _API],
                         ["-x", "c++", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-O2", "-ffp-contract=off"]),
     # (step.hpp's algebra again: the sharded muse! loop takes the same step as muse_run)
     "muse_comm": ("muse_comm.cpp", [_API, os.path.join(CSRC, "shm_gather.hpp"), os.path.join(CSRC, "args.hpp"), os.path.join(CSRC, "step.hpp"), _SWITCHES, _HOST_LOOP, _HANDOFF],
@@ -155,9 +155,10 @@ def model_lib_path(name):
     return os.path.join(model_out_dir(), f"libmuse_hip_model_{name}.so")
 
 
-def build_model_library(header, name, force=False, verbose=False):
+def build_model_library(header, name, force=False, verbose=False, defines=()):
     """Compile (if missing or stale) the engine library of the model in `header`; returns its path (in-tree, next to
-    libmuse_hip.so, so that it travels with a snapshot of the repository)."""
+    libmuse_hip.so, so that it travels with a snapshot of the repository).  `defines`: further -D switches of a comparison build
+    under a name of its own (tools/model_exp_bench.py: -DMUSE_MODEL_EXP_PLAIN, csrc/user_model.hpp)."""
     header = os.path.abspath(header)
     if not os.path.exists(header):
         raise FileNotFoundError(header)
@@ -166,7 +167,7 @@ def build_model_library(header, name, force=False, verbose=False):
     if force or _stale(path, deps):
         with _BuildLock(path):
             if force or _stale(path, deps):     # (another process may have built it while this one waited)
-                build_extension(defines=[f'-DMUSE_USER_MODEL_HEADER="{header}"', "-I" + INCLUDE_DIR], lib_path=path, verbose=verbose)
+                build_extension(defines=[f'-DMUSE_USER_MODEL_HEADER="{header}"', "-I" + INCLUDE_DIR] + list(defines), lib_path=path, verbose=verbose)
     return path
 
 

@@ -329,6 +329,8 @@ struct LaunchShape {
                  // SmoothLinkModel), with noise vectors -- unit ones when none were set -- and weights as `noise` has them; map kernels only
     size_t lds;
     void* done_event;  // hipEvent_t (or null) that the launch itself signals on completion: no separate event packet
+    int* scratch_query = nullptr;  // not null: a QUERY -- the map kernel of this shape reports its private segment per lane (the bytes its
+                                   // spilled registers take) here and nothing is launched (muse_engine.cpp, map_unfit_mask)
 };
 hipError_t launch_solver(const LaunchShape& s, const BatchArgs& a, hipStream_t stream);
 // (taps: the stencil model with the launch's own weights, BatchArgs::taps; noisy: with its own noise vectors as well; link: and its response)

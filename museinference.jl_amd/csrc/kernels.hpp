@@ -814,6 +814,12 @@ constexpr int kJacobiScratchLimit = 256;  // bytes per lane (tools/regs.py, LIBR
 template <class Model, class Place, bool IMPLICIT = false>
 static hipError_t launch_one(const LaunchShape& s, const BatchArgs& a, hipStream_t stream) {
     auto kern = map_score_kernel<Model, Place, IMPLICIT>;
+    if (s.scratch_query) {   // (args.hpp, LaunchShape: a query, no launch)
+        hipFuncAttributes at;
+        const hipError_t e = hipFuncGetAttributes(&at, (const void*)kern);
+        if (e == hipSuccess) *s.scratch_query = (int)at.localSizeBytes;
+        return e;
+    }
     // per instantiation AND per device (the attribute belongs to the device's copy of the function): raised once, not per launch
     static size_t lds_allowed[kMaxDevices];
     int dev = 0;

@@ -71,6 +71,7 @@ struct muse_ctx {
     LaneState* lane = nullptr;    // the lane the current call works on: lanes[0] at every entry (check_ctx) and every return
     int nlanes = 1;
     int model = 0, ntheta = 1, device = 0, placement = -1, num_cus = 0;
+    unsigned map_unfit = 0;   // bit pl: the map kernel of resident placement pl keeps its state in scratch (map_unfit_mask): it streams instead
     int64_t N = 0, ld = 0;
     int64_t bnd[kBigTheta + 1] = {0};
     hipStream_t own_stream = nullptr;   // lane 0's stream until muse_set_stream replaces it
@@ -226,19 +227,27 @@ static bool use_cluster(const muse_ctx* c) { return c->split >= 2 || c->N >= kCl
 
 // Workgroup size is a function of N alone (256 threads for N <= 512, else 512), so that the
 // streaming and the resident policy reduce in the same order and give bitwise equal results.
-static int choose_place(const muse_ctx* c) {
+static int choose_place_as(const muse_ctx* c, int placement) {
     const bool small = c->N <= 512;
     // cluster mode: for the stencil model the neighbours owned by other workgroups become visible through
     // the agent-scope release/acquire of the cluster reduction that ends every pass (pass_barrier where a
     // pass has no reduction)
     const bool big = c->ntheta > kMaxTheta;  // the big tier (args.hpp, BigTheta) runs in the streaming placements
-    if (c->split >= 2 && c->split <= 8 && !stencil_ctx(c) && c->placement != 0 && c->N <= kMaxResidentN && !big)
+    if (c->split >= 2 && c->split <= 8 && !stencil_ctx(c) && placement != 0 && c->N <= kMaxResidentN && !big)
         return c->split == 2 ? P_CR2 : (c->split == 4 ? P_CR4 : P_CR8);
     if (use_cluster(c)) return P_C256;
-    if (stencil_ctx(c) || c->placement == 0 || c->N > kMaxResidentN || big) return small ? P_S256 : P_S512;
+    if (stencil_ctx(c) || placement == 0 || c->N > kMaxResidentN || big) return small ? P_S256 : P_S512;
     if (small) return P_R256x1;
     if (c->N <= 4096) return P_R512x4;
     return P_R512x10;
+}
+// ... unless the map kernel of that resident placement is one whose state the compiler spilled (a user's header can do that: an
+// exponential per element in a four-block model of the two-parameter family; map_unfit_mask below, read when the context is
+// created): it runs the streaming placement the caller could have asked for -- the same bits by the rule above -- and
+// muse_placement_info says so.  No library of the built-in models and no kernel within the product's bound is ever routed.
+static int choose_place(const muse_ctx* c) {
+    const int pl = choose_place_as(c, c->placement);
+    return ((c->map_unfit >> pl) & 1u) ? choose_place_as(c, 0) : pl;
 }
 // Which instantiation a launch of placement `pl` gets: the big tier's (args.hpp, BigTheta: tables from the kernarg segment, blocks
 // by arithmetic, block sums in chunks) for more than kMaxTheta components -- and for 2..kMaxTheta components of an elementwise
@@ -249,6 +258,42 @@ static bool tier_big(const muse_ctx* c, int pl, int nmaps) {
     if (c->ntheta > kMaxTheta) return true;
     if (kPairModel) return false;   // (one tier: models.hpp, UserModel of the two-parameter family)
     return !c->sw.no_big_tier && c->ntheta > 1 && !stencil_ctx(c) && nmaps <= 1 && (pl == P_S256 || pl == P_S512 || pl == P_C256);
+}
+// The fence of the resident MAP kernels, as loop_usable fences the loop kernel: a map kernel beyond the product's bound on scratch
+// (tools/regs.py, LIBRARY_SCRATCH_LIMIT; the regime in which spill code was seen to lose uniform values held across the solve) is
+// not launched.  Bit pl of the result: resident placement pl is such a kernel for this (model, ntheta).  Read from the code object
+// once per device and tier (hipFuncGetAttributes: no launch); libraries of user-supplied elementwise models only -- the kernels of
+// libmuse_hip.so are checked when it is built (tests/test_kernel_resources.py).
+static unsigned map_unfit_mask(int device, int model, int ntheta) {
+#if defined(MUSE_USER_MODEL_HEADER) && !defined(MUSE_MODEL_RESPONSE)
+    constexpr int kMapScratchLimit = 256;
+    // (filled without a lock while muse_ctx_create may run on several threads: every thread that finds an entry empty computes the
+    //  same word from the same code object and stores it whole -- a repeated query, never a wrong answer)
+    static unsigned seen[64][kMaxTheta + 1];   // 0: not yet; bit 31: known
+    if (device < 0 || device >= 64 || ntheta < 1 || ntheta > kMaxTheta) return 0;
+    if (!seen[device][ntheta]) {
+        unsigned mask = 0x80000000u;
+        static const BatchArgs none = BatchArgs();
+        for (int pl : {P_R256x1, P_R512x4, P_R512x10, P_CR2, P_CR4, P_CR8}) {
+            int bytes = 0;
+            LaunchShape shape;
+            shape.model = model; shape.ntheta = ntheta; shape.place = pl; shape.grid = 1; shape.implicit = false; shape.jacobi = false;
+            shape.big = false; shape.lds_s = false; shape.taps = false; shape.noise = false; shape.link = false; shape.lds = 0;
+            shape.done_event = nullptr;
+            shape.scratch_query = &bytes;
+            if (launch_solver(shape, none, nullptr) != hipSuccess) {
+                (void)hipGetLastError();
+                continue;   // (no answer: the placement stays as it is)
+            }
+            if (bytes > kMapScratchLimit) mask |= 1u << pl;
+        }
+        seen[device][ntheta] = mask;
+    }
+    return seen[device][ntheta] & 0x7fffffffu;
+#else
+    (void)device; (void)model; (void)ntheta;
+    return 0;
+#endif
 }
 static bool ncache_applies(const muse_ctx* c) {
     return !c->sw.no_ncache && choose_place(c) == P_R512x10;
@@ -691,6 +736,7 @@ int muse_ctx_create(int model, int64_t N, int ntheta, int device, muse_ctx** out
             c->bnd[k] = ((int64_t)kk * N + nb - 1) / nb;
         }
     }
+    c->map_unfit = map_unfit_mask(device, model, ntheta);
     HIPCHK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
     {
         const int rc = use_lane(c, 0);

@@ -142,6 +142,14 @@ class ElementwiseModel:
             self._library = _build.build_model_library(self.header, self.library_name, force=force)
         return self._library
 
+    def use_library(self, path):
+        """Load `path` -- a comparison build of this model's header under another name (build_model_library(header, name,
+        defines=[...]): tools/model_exp_bench.py) -- instead of the library library() would build."""
+        if not os.path.exists(path):
+            raise FileNotFoundError(path)
+        self._library = os.path.abspath(path)
+        return self
+
     def __repr__(self):
         return f"ElementwiseModel({self.name!r}, {self.header!r})"
 
