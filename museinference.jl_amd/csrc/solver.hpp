@@ -82,6 +82,11 @@ struct PairState<true> {
 // VGPR launder, the code they always had.
 template <class Model, class Place>
 constexpr bool uniform_linesearch() { return !(Place::kResident && Place::kXgLds && Model::MAXB > 1); }
+// The all-reduce combines a wave's four row totals in vector registers (reduce.hpp, ROW_BCAST).  The streaming cluster placement of
+// the elementwise models with eight components is at the register file's limit: there the vector form's K temporaries cost two
+// more spilled VGPRs (20 -> 22, 60 -> 68 bytes of scratch in the library build): that entry point keeps the v_readlane form.
+template <class Model, class Place>
+constexpr bool row_broadcast() { return !(Place::kCluster && !Place::kResident && !Model::kStencil && Model::MAXB == 8); }
 template <class Model, class Place, bool UNIFORM_LS = uniform_linesearch<Model, Place>()>
 struct Solver : PairState<Model::kPair> {
     static constexpr int T = Place::T, EPT = Place::EPT, U = Place::U, MAXB = Model::MAXB;
@@ -230,7 +235,7 @@ struct Solver : PairState<Model::kPair> {
         // stencil model in a cluster: this pass's (write-through) stores have left every wave before the workgroup's
         // barrier inside block_allreduce, i.e. before wave 0 publishes the epoch the other members wait for
         if constexpr (Place::kCluster && Model::kStencil) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        block_allreduce<T, KS, KM, !Model::kStencil>(sv, mv, red, parity, tid);
+        block_allreduce<T, KS, KM, !Model::kStencil, row_broadcast<Model, Place>()>(sv, mv, red, parity, tid);
         if constexpr (Place::kCluster) cluster_exchange<KS, KM>(sv, mv);
     }
     // Orders this pass's vector stores before the next pass's neighbour reads (stencil model).

@@ -1,6 +1,8 @@
 // VALU issue/latency probe (development aid): every workgroup runs C independent chains of dependent fp64 FMAs (mode 0),
 // 64-bit integer multiply-adds v_mad_u64_u32 (mode 1), fp64 multiplies (mode 2), fp64 adds (mode 3) or 32-bit integer
-// xors (mode 4) or three-input bitwise ops v_bitop3_b32 with the a ^ b ^ c truth table (mode 5: three vector sources, mode 6: one scalar source), and reads s_memtime (shader clocks; s_memrealtime, 100 MHz, gives the clock) around the loop.
+// xors (mode 4) or three-input bitwise ops v_bitop3_b32 with the a ^ b ^ c truth table (mode 5: three vector sources, mode 6: one scalar source)
+// or gfx950's row swaps v_permlane16_swap_b32 / v_permlane32_swap_b32 of two registers (modes 7 and 8: through the builtins, so that the
+// compiler places the wait states the instruction needs after a VALU write of its operands -- they are part of its cost), and reads s_memtime (shader clocks; s_memrealtime, 100 MHz, gives the clock) around the loop.
 // Prints shader cycles per instruction per wave at 1 and 2 waves per SIMD.  usage: clockprobe [iters]
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -35,12 +37,14 @@ __global__ void __launch_bounds__(1024) probe(unsigned long long* out, int iters
                 if (MODE == 4) asm volatile("v_xor_b32 %0, %0, %1" : "+v"(x[c]) : "v"(0x9E3779B9u));
                 if (MODE == 5) asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:0x96" : "+v"(x[c]) : "v"(0x9E3779B9u), "v"(y[c]));
                 if (MODE == 6) asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:0x96" : "+v"(x[c]) : "v"(y[c]), "s"(sk));   // one scalar source, as the round's key word
+                if (MODE == 7) { const auto p = __builtin_amdgcn_permlane16_swap(x[c], y[c], false, false); x[c] = p[0]; y[c] = p[1]; }
+                if (MODE == 8) { const auto p = __builtin_amdgcn_permlane32_swap(x[c], y[c], false, false); x[c] = p[0]; y[c] = p[1]; }
             }
         }
     }
     asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(t1), "=s"(r1)::"memory");
     double acc = 0;
-    for (int c = 0; c < C; ++c) acc += a[c] + (double)m[c] + (double)x[c];
+    for (int c = 0; c < C; ++c) acc += a[c] + (double)m[c] + (double)x[c] + (double)y[c];
     if (threadIdx.x == 0) {
         out[blockIdx.x * 4 + 0] = t1 - t0;
         out[blockIdx.x * 4 + 1] = r1 - r0;
@@ -91,5 +95,7 @@ int main(int argc, char** argv) {
     run<4, 1>(d, iters, "v_xor_b32"); run<4, 4>(d, iters, "v_xor_b32");
     run<5, 1>(d, iters, "v_bitop3_b32"); run<5, 4>(d, iters, "v_bitop3_b32");
     run<6, 1>(d, iters, "v_bitop3_b32 vvs"); run<6, 4>(d, iters, "v_bitop3_b32 vvs");
+    run<7, 1>(d, iters, "v_permlane16_swap"); run<7, 4>(d, iters, "v_permlane16_swap");
+    run<8, 1>(d, iters, "v_permlane32_swap"); run<8, 4>(d, iters, "v_permlane32_swap");
     return 0;
 }
