@@ -70,7 +70,14 @@ map_score_kernel(const BatchArgs /*read via the kernarg segment*/) {
         for (int w = tid; w < (int)(kArgsHeadBytes / 4); w += T) dst[w] = kp[w];  // (not the trailing maps[]: see load_problem_theta)
         if (tid == 0) ticket[2] = 0;   // (solver.hpp, wait_fiducial: the tag of the fiducial MAP this workgroup has seen published)
     }
+#ifdef MUSE_STAMPS   // the prologue's split (detail mode, below): the kernarg words have landed / the barrier behind the LDS copy
+    unsigned long long t_landed, t_synced;
+    asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_landed)::"memory");
+#endif
     __syncthreads();
+#ifdef MUSE_STAMPS
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_synced)::"memory");
+#endif
     const BatchArgs& a = *reinterpret_cast<const BatchArgs*>(args_lds);
     double* exch = args_lds + kArgsDoubles;   // cluster placements: [kMaxCluster][8] values of the epoch's exchange
     double* lds_x = exch + (Place::kCluster ? kMaxCluster * 8 : 0);  // [ld + 2]: elements, dummy slot (index ld), pad
@@ -155,27 +162,75 @@ map_score_kernel(const BatchArgs /*read via the kernarg segment*/) {
         // index (the host launches grid <= nproblems), and the ticket of the NEXT problem (p = grid + ticket) is drawn when
         // the current one begins -- the atomic's round trip (~1.5 k cycles, three of them per workgroup at configs[1]) is
         // over long before its result is looked at.
+        // The hand-over has no barrier of its own (elementwise models).  Thread 0 stores the ticket into the LDS word
+        // ticket[nth & 1] (nth: how many problems this workgroup has taken) in front of begin()'s last barrier, which every wave
+        // passes in every problem; every wave reads the word at the problem's end, behind that barrier.  The word of parity q is
+        // written again two problems later, by a thread that has passed a barrier of the problem in between -- and every wave
+        // arrives at that barrier only after it has read the word at the end of the problem before.  So no wave reads a word
+        // before it is written or after it is rewritten, and the next problem's first instruction follows the finished one's
+        // last: the MAP's stores (its slot is read by nothing in the next problem) drain under the next problem's generator.
+        // Nothing else in LDS needs the barriers that stood here: before its first barrier begin() writes only the sampling
+        // table (read inside begin() alone, which every wave has left when any wave enters the next one) and the thread's own
+        // x / g slots.  The stencil model's threads read their neighbours' elements: it keeps the two barriers.
+        // The reduction scratch: a placement without x and g in LDS evaluates inside begin()'s sampler pass and reduces BEFORE that
+        // barrier, so its reductions go on alternating between the scratch's two halves ACROSS problems (red_parity): the first
+        // reduction of a problem then never writes the half that a wave still in the last reduction of the problem before reads.
+        // (The atomic stays the flat one it was.  On a global pointer the compiler's wave-aggregation of atomics takes the add up and
+        //  waits for the result -- vmcnt(0), the finished problem's stores with it -- right behind the issue; a global atomic at an
+        //  address laundered into a vector register escapes that, and measured the same as the flat one: HISTORY.md section 8.)
+        constexpr bool kReducesInBegin = !Model::kStencil && !(Place::kResident && Place::kXgLds);
+        int red_parity = 0;
         int p = (int)blockIdx.x;
-        for (;;) {
+        for (int nth = 0;; ++nth) {
             int next = 0;
             if (tid == 0) next = atomicAdd(a.work_counter, 1);
 #ifdef MUSE_STAMPS
-            if (tid == 0 && a.stamps && p < (int)gridDim.x) a.stamps[(size_t)p * 16 + 8] = t_entry;  // kernel entry
+            // (detail mode -- debug bit 10, tools/stamps.py --: slots 10-15 of a problem's row carry the split of the prologue
+            //  and of the hand-over instead of the line search's; slot 8 is begin()'s "sampler loop end" in both modes)
+            const bool detail = tid == 0 && a.stamps && (a.debug & 1024);
+            if (detail && p < (int)gridDim.x) {
+                a.stamps[(size_t)p * 16 + 15] = t_entry;   // kernel entry
+                a.stamps[(size_t)p * 16 + 10] = t_landed;  // the kernarg words are in registers
+                a.stamps[(size_t)p * 16 + 11] = t_synced;  // the barrier behind the LDS copy of the arguments
+            }
 #endif
             load_problem_theta<!Model::kStencil>(a, args_lds, p, tid);
+#ifdef MUSE_STAMPS
+            if (detail && p < (int)gridDim.x) {
+                unsigned long long t;
+                asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+                a.stamps[(size_t)p * 16 + 12] = t;         // (pack_blocks, the ticket's atomic issued,) load_problem_theta
+            }
+            const int p_done = p;
+#endif
+            int* const word = ticket + (nth & 1);
             {
                 Solver<Model, Place> sv(a, tid, red, shs);
                 sv.pk[0] = pk0;
                 sv.pk[1] = pk1;
+                if constexpr (!Model::kStencil) {
+                    sv.tk_word = word;
+                    sv.tk_val = next;
+                }
+                if constexpr (kReducesInBegin) sv.parity = red_parity;
                 if constexpr (IMPLICIT && Model::kPair) sv.template run_implicit_pair<JACOBI>(p, wg_scratch, lds_x, lds_g);
                 else if constexpr (IMPLICIT) sv.template run_implicit<JACOBI>(p, wg_scratch, lds_x, lds_g);
                 else sv.run(p, wg_scratch, lds_x, lds_g);
+                if constexpr (kReducesInBegin) red_parity = sv.parity;
             }
-            // (raw barriers for the elementwise models: the MAP's stores keep draining while the next problem starts)
-            wg_barrier<!Model::kStencil>();
-            if (tid == 0) ticket[0] = next;
-            wg_barrier<!Model::kStencil>();
-            p = (int)gridDim.x + (__builtin_amdgcn_readfirstlane(ticket[0]) - a.ticket_base);
+            if constexpr (Model::kStencil) {
+                __syncthreads();
+                if (tid == 0) *word = next;
+                __syncthreads();
+            }
+            p = (int)gridDim.x + (__builtin_amdgcn_readfirstlane(*word) - a.ticket_base);
+#ifdef MUSE_STAMPS
+            if (detail) {
+                unsigned long long t;
+                asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+                a.stamps[(size_t)p_done * 16 + 14] = t;    // hand-over: the next problem's index is known
+            }
+#endif
             if (p >= a.nproblems) break;
         }
         clock_stamp(1);

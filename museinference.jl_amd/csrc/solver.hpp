@@ -124,6 +124,11 @@ struct Solver : PairState<Model::kPair> {
     bool cl_aborted;           // a bounded wait expired: stop waiting
     double* cl_part;           // this cluster's partial slots [2][csize][8] / granules [2][csize][8][2]
     double* exch;              // LDS [kMaxCluster][8]: the epoch's values of every member (granule exchange)
+    // The map kernel's hand-over (kernels.hpp, the dynamic deal): thread 0 holds the ticket of the workgroup's NEXT problem and
+    // stores it into this LDS word in front of begin()'s last barrier -- the one barrier every wave passes in every problem,
+    // whatever its kind.  nullptr: nothing to publish (the cluster placements, the loop kernel).
+    int* tk_word;
+    int tk_val;
 
     __device__ Solver(const BatchArgs& a_, int tid_, double* red_, double* shs) : a(a_), tid(tid_), red(red_), parity(0) {
         sh_rho = shs;
@@ -138,6 +143,8 @@ struct Solver : PairState<Model::kPair> {
         cl_aborted = false;
         cl_part = nullptr;
         exch = nullptr;
+        tk_word = nullptr;
+        tk_val = 0;
         gen.p = -1;
         gen.trip = 0;
         gen.active = false;
@@ -253,7 +260,9 @@ struct Solver : PairState<Model::kPair> {
     // buffer of their own and no output is computed from them.
     __device__ __forceinline__ void stamp(int p, int k) const {
 #ifdef MUSE_STAMPS
-        if (tid == 0 && a.stamps) {
+        // (detail mode, debug bit 10: slots 10-15 hold the map kernel's prologue and hand-over split -- kernels.hpp -- and the line
+        //  search's stamps stay out of them)
+        if (tid == 0 && a.stamps && !(k >= 10 && (a.debug & 1024))) {
             unsigned long long t;
             asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
             a.stamps[(size_t)p * 16 + k] = t;
@@ -1607,6 +1616,7 @@ struct Solver : PairState<Model::kPair> {
                         }
                     }
                 }
+                stamp(p, 8);   // sampler loop end (the start's pick-up follows; stamp 9 behind it)
                 z.clear();
                 s.clear();
                 if (z_loaded) {
@@ -1615,12 +1625,14 @@ struct Solver : PairState<Model::kPair> {
                         z.set(2 * j, 0, zw[j][0]);
                         z.set(2 * j + 1, 0, zw[j][1]);
                     }
+                } else if (d.z0_mode == Z0_ZERO) {
+                    // (the start is decided ONCE per problem -- it is workgroup-uniform --, not per element: inside the element
+                    //  loop the compiler kept a ladder of scalar branches with register copies at every merge for each of the
+                    //  thread's 2 * EPT slots, ~4.4 k cycles per problem at EPT = 10.  z.clear() above IS the zero start.)
+                } else if (d.z0_mode == Z0_TRUE) {
+                    for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) { z.set(jj, i, g.get(jj, i)); });
                 } else {
-                    for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) {
-                        if (d.z0_mode == Z0_ZERO) z.set(jj, i, 0.0);
-                        else if (d.z0_mode == Z0_TRUE) z.set(jj, i, g.get(jj, i));
-                        else z.set(jj, i, z0src.get(jj, i));
-                    });
+                    for_elems<T, EPT, U>(ld, tfirst, ps(), [&](int jj, int i) { z.set(jj, i, z0src.get(jj, i)); });
                 }
             } else {
                 x.clear(); g.clear(); z.clear(); s.clear();
@@ -1806,6 +1818,15 @@ struct Solver : PairState<Model::kPair> {
             }
             pf.p = -1;
             pf.g_pending = false;
+        }
+        // (the next problem's ticket: its atomic was issued before this problem's first instruction and has long returned)
+        // (every wave waits for it HERE, outside the one-thread branch -- the empty asm is a use of the register: a wait inside the
+        //  branch alone left the register pending at the branch's merge, and the compiler then put s_waitcnt vmcnt(0) at the
+        //  problem loop's header, where it also waited for the finished problem's MAP stores)
+        if (tk_word != nullptr) {
+            int tk = tk_val;
+            asm volatile("" : "+v"(tk));
+            if (tid == 0) *tk_word = tk;
         }
         stamp(p, 9);
         if constexpr (Model::kStencil) pass_barrier();  // x (and the start z) complete before neighbours read them
