@@ -70,7 +70,9 @@ HAND_N, HAND_SIMS, HAND_ATOL = 1001, 600, 1e-3
 
 
 def test_handover_equals_one_problem_per_launch(gpu, M):
-    """600 problems, more than compute units: workgroups take one, two or three of them.  Every problem must equal the same
+    """600 problems on a grid of two workgroups per compute unit (PlaceResident<512, 4>): on a card of 256 compute units 512
+    workgroups take their first problem and 88 tickets are handed over, so some workgroups take a second problem and none needs
+    a third -- the chains of three and more are tests/test_gpu_handover_matrix.py's.  Every problem must equal the same
     simulation solved in a launch of its own."""
     gr, ir, zr = _reference(M, HAND_N, HAND_SIMS, M.Z0_ZERO, HAND_ATOL)
     prob = _new(M, HAND_N)
