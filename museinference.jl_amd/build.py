@@ -16,8 +16,9 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libmuse_hip.so")
 OBJ_DIR = os.path.join(_HERE, "build")
 _API = os.path.join(_HERE, "..", "include", "muse_hip.h")
-_KERNEL_HEADERS = [os.path.join(CSRC, h) for h in ("rng.hpp", "args.hpp", "vec.hpp", "reduce.hpp", "models.hpp", "user_model.hpp", "model_math.hpp", "solver.hpp",
+_KERNEL_HEADERS = [os.path.join(CSRC, h) for h in ("rng.hpp", "args.hpp", "tiers.hpp", "vec.hpp", "reduce.hpp", "models.hpp", "user_model.hpp", "model_math.hpp", "solver.hpp",
                                                     "step.hpp", "kernels.hpp")]
+_ARGS = [os.path.join(CSRC, "args.hpp"), os.path.join(CSRC, "tiers.hpp")]   # (args.hpp includes tiers.hpp: the tiers' bounds)
 _SWITCHES = os.path.join(CSRC, "switches.hpp")
 _HOST_LOOP = os.path.join(CSRC, "host_loop.h")      # host only: the muse! loop muse_run and muse_run_sharded share
 _HANDOFF = os.path.join(CSRC, "comm_handoff.h")     # host only: the RCCL transport's caller -> worker queue
@@ -34,10 +35,10 @@ UNITS = {
     **{f"kernels_part{n}": ("kernels_part.hip", _KERNEL_HEADERS + [_API], _DEVICE_FLAGS + [f"-DMUSE_PART={n}"]) for n in range(KERNEL_PARTS)},
     # host code: plain C++ against the HIP runtime API (no device pass)
     # (-ffp-contract=off here too: step.hpp's algebra must round on the host exactly as in the step kernel)
-    "muse_engine": ("muse_engine.cpp", [os.path.join(CSRC, "args.hpp"), os.path.join(CSRC, "step.hpp"), os.path.join(CSRC, "user_model.hpp"), os.path.join(CSRC, "model_math.hpp"), _SWITCHES, _HOST_LOOP, _API],
+    "muse_engine": ("muse_engine.cpp", _ARGS + [os.path.join(CSRC, "step.hpp"), os.path.join(CSRC, "user_model.hpp"), os.path.join(CSRC, "model_math.hpp"), _SWITCHES, _HOST_LOOP, _API],
                         ["-x", "c++", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-O2", "-ffp-contract=off"]),
     # (step.hpp's algebra again: the sharded muse! loop takes the same step as muse_run)
-    "muse_comm": ("muse_comm.cpp", [_API, os.path.join(CSRC, "shm_gather.hpp"), os.path.join(CSRC, "args.hpp"), os.path.join(CSRC, "step.hpp"), _SWITCHES, _HOST_LOOP, _HANDOFF],
+    "muse_comm": ("muse_comm.cpp", [_API, os.path.join(CSRC, "shm_gather.hpp")] + _ARGS + [os.path.join(CSRC, "step.hpp"), _SWITCHES, _HOST_LOOP, _HANDOFF],
                       ["-x", "c++", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-O2", "-ffp-contract=off"]),
 }
 COMMON_FLAGS = ["-std=c++17", "-fPIC", "-Wno-unused-value"]
@@ -191,8 +192,7 @@ _LBFGS_SOURCE = os.path.join(LBFGS_DIR, "lbfgs_kernels.hip")
 _LBFGS_DEPS = [_LBFGS_SOURCE, os.path.join(LBFGS_DIR, "lbfgs_control.hpp"), os.path.join(LBFGS_DIR, "lbfgs_advance.hpp"),
                os.path.join(LBFGS_DIR, "cg_control.hpp"), os.path.join(LBFGS_DIR, "cg_advance.hpp"), os.path.join(LBFGS_DIR, "cg_kernels.hpp"),
                os.path.join(LBFGS_DIR, "pcg_control.hpp"), os.path.join(LBFGS_DIR, "pcg_advance.hpp"), os.path.join(LBFGS_DIR, "pcg_kernels.hpp"),
-               os.path.join(LBFGS_DIR, "normals_kernels.hpp"), _LBFGS_API, os.path.join(CSRC, "reduce.hpp"), os.path.join(CSRC, "args.hpp"),
-               os.path.join(CSRC, "rng.hpp")]
+               os.path.join(LBFGS_DIR, "normals_kernels.hpp"), _LBFGS_API, os.path.join(CSRC, "reduce.hpp"), os.path.join(CSRC, "rng.hpp")] + _ARGS
 
 
 def lbfgs_declared_symbols():

@@ -5,14 +5,13 @@
 #include <stdint.h>
 
 #include "../../include/muse_hip.h"
+#include "tiers.hpp"   // kMaxTheta, kBigTheta
 
 namespace muse {
 
 
 constexpr int kM = 10;         // L-BFGS memory (Optim.LBFGS default m)
 constexpr int kMaxIter = 1000;  // Optim.Options default iterations
-constexpr int kMaxTheta = MUSE_MAX_THETA;
-constexpr int kBigTheta = MUSE_MAX_THETA_EXT;  // ntheta in (kMaxTheta, kBigTheta]: the "big" tier (BigTheta below)
 constexpr int kResultAreas = 4;
 constexpr int kMaxCluster = 16;
 constexpr int kStencilTaps = 3;                          // window of the stencil model's operator: symmetric, periodic
@@ -314,21 +313,21 @@ struct LoopArgs {
 };
 
 // launch shims of muse_kernels.hip (the only translation unit that holds device code)
-struct LaunchShape {
-    int model, ntheta, place, grid;
-    bool implicit;
-    bool jacobi;  // implicit: the kernels with the preconditioned CG loop and the run-time CG keywords (MUSE_IMPLICIT_PL_JACOBI, or
+struct LaunchShape {   // (muse_engine.cpp, shape_of: a context's shape in a placement; a site sets what differs from these defaults)
+    int model = -1, ntheta = 0, place = 0, grid = 1;
+    bool implicit = false;
+    bool jacobi = false;  // implicit: the kernels with the preconditioned CG loop and the run-time CG keywords (MUSE_IMPLICIT_PL_JACOBI, or
                   // any keyword the default kernels do not read); elementwise models only
-    bool big;    // the big tier's instantiation (BigTheta): ntheta > kMaxTheta, or 2..kMaxTheta components of an elementwise model in a
+    bool big = false;    // the big tier's instantiation (BigTheta): ntheta > kMaxTheta, or 2..kMaxTheta components of an elementwise model in a
                  // streaming placement (muse_engine.cpp, tier_big: the same bits, 2.4x faster than the small tiers' streaming passes)
-    bool lds_s;  // stencil model in a cluster: the search direction in LDS (vec.hpp, LdsMirror)
-    bool taps;   // stencil model: the operator's weights are the launch's (BatchArgs::taps), not the built-in literals
-    bool noise;  // stencil model: the launch carries the context's noise vectors (BatchArgs::consts[0 .. 1] = {omega, s}; models.hpp,
+    bool lds_s = false;  // stencil model in a cluster: the search direction in LDS (vec.hpp, LdsMirror)
+    bool taps = false;   // stencil model: the operator's weights are the launch's (BatchArgs::taps), not the built-in literals
+    bool noise = false;  // stencil model: the launch carries the context's noise vectors (BatchArgs::consts[0 .. 1] = {omega, s}; models.hpp,
                  // SmoothNoiseModel) and its weights -- (1/2, 1/4) when none were set -- in BatchArgs::taps
-    bool link;   // stencil model: the launch carries the context's response coefficients as well (BatchArgs::link = {a2, a3}; models.hpp,
+    bool link = false;   // stencil model: the launch carries the context's response coefficients as well (BatchArgs::link = {a2, a3}; models.hpp,
                  // SmoothLinkModel), with noise vectors -- unit ones when none were set -- and weights as `noise` has them; map kernels only
-    size_t lds;
-    void* done_event;  // hipEvent_t (or null) that the launch itself signals on completion: no separate event packet
+    size_t lds = 0;
+    void* done_event = nullptr;  // hipEvent_t (or null) that the launch itself signals on completion: no separate event packet
     int* scratch_query = nullptr;  // not null: a QUERY -- the map kernel of this shape reports its private segment per lane (the bytes its
                                    // spilled registers take) here and nothing is launched (muse_engine.cpp, map_unfit_mask)
 };

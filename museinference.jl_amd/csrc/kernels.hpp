@@ -1009,92 +1009,75 @@ hipError_t loop_place(const LaunchShape& s, const LoopCall& c) {
     return hipErrorNotSupported;  // streaming and cluster placements: the host loop (muse_run) runs those
 }
 
-// Which models' kernels live in which translation unit (kernels_part.hip, -DMUSE_PART=n); muse_kernels.hip declares them `extern`.
-#define MUSE_INSTANTIATE_ELEMENTWISE(X, M)                                                          \
-    X template hipError_t launch_place<M>(const LaunchShape&, const BatchArgs&, hipStream_t);       \
-    X template hipError_t launch_place_implicit<M>(const LaunchShape&, const BatchArgs&, hipStream_t); \
-    X template hipError_t loop_place<M>(const LaunchShape&, const LoopCall&);
-#define MUSE_INSTANTIATE_STENCIL(X, M)                                                              \
-    X template hipError_t launch_place<M>(const LaunchShape&, const BatchArgs&, hipStream_t);       \
-    X template hipError_t launch_place_implicit<M>(const LaunchShape&, const BatchArgs&, hipStream_t);
-// (the map kernels alone: a model whose implicit-differentiation pass the engine refuses, models.hpp, SmoothLinkModel)
-#define MUSE_INSTANTIATE_STENCIL_MAP(X, M) X template hipError_t launch_place<M>(const LaunchShape&, const BatchArgs&, hipStream_t);
-#define MUSE_INSTANTIATE_BIG_MAP(X, M) X template hipError_t launch_place_big<M>(const LaunchShape&, const BatchArgs&, hipStream_t);
-#define MUSE_INSTANTIATE_BIG(X, M)                                                                  \
-    X template hipError_t launch_place_big<M>(const LaunchShape&, const BatchArgs&, hipStream_t);   \
-    X template hipError_t launch_place_implicit<M>(const LaunchShape&, const BatchArgs&, hipStream_t);
-#if defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_RESPONSE)
-// A response behind the stencil operator (include/muse_model.h, MUSE_MODEL_RESPONSE): the map kernels the link model has -- the
-// streaming and cluster placements in the tiers of 2, 4 and 8 components, the big tier -- and, for a header that states phi''
-// (MUSE_MODEL_RESPONSE_SECOND), the implicit differentiation's (solver.hpp, run_implicit, its response fork).  No loop kernels: the stencil streams.
-#ifdef MUSE_MODEL_RESPONSE_SECOND
-#define MUSE_INSTANTIATE_RESPONSE(X, M) MUSE_INSTANTIATE_STENCIL(X, M)
-#define MUSE_INSTANTIATE_RESPONSE_BIG(X, M) MUSE_INSTANTIATE_BIG(X, M)
+// ---- a model's kernels: they follow from the model ------------------------------------------------------------------------------
+// The big tier (MAXB > kMaxTheta) streams and has no loop kernel; the implicit-differentiation pass needs second derivatives -- every
+// built-in model but the one with a link, whose pass the engine refuses, and a user's header that states them (include/muse_model.h).
+// launch_model / loop_model are what muse_kernels.hip's dispatch calls and what a unit of kernels_part.hip instantiates.  (The map
+// branch is named before the implicit one: the order of instantiation moves a kernel's code.)
+template <class Model>
+constexpr bool model_has_implicit() {
+#if !defined(MUSE_USER_MODEL_HEADER)
+    return !link_model<Model>();
+#elif defined(MUSE_MODEL_RESPONSE) ? defined(MUSE_MODEL_RESPONSE_SECOND) : defined(MUSE_MODEL_PAIR) ? defined(MUSE_MODEL_PAIR_SECOND) : defined(MUSE_MODEL_SECOND)
+    return true;
 #else
-#define MUSE_INSTANTIATE_RESPONSE(X, M) MUSE_INSTANTIATE_STENCIL_MAP(X, M)
-#define MUSE_INSTANTIATE_RESPONSE_BIG(X, M) MUSE_INSTANTIATE_BIG_MAP(X, M)
+    return false;
 #endif
-#define MUSE_PART_0(X) MUSE_INSTANTIATE_RESPONSE(X, UserResponseModel<2>)
-#define MUSE_PART_1(X) MUSE_INSTANTIATE_RESPONSE(X, UserResponseModel<4>)
-#define MUSE_PART_2(X) MUSE_INSTANTIATE_RESPONSE(X, UserResponseModel<kMaxTheta>)
-#define MUSE_PART_3(X) MUSE_INSTANTIATE_RESPONSE_BIG(X, UserResponseModel<kBigTheta>)
-#define MUSE_PART_4(X)
-#define MUSE_PART_5(X)
-#define MUSE_PART_6(X)
-#define MUSE_PART_7(X)
+}
+template <class Model>
+hipError_t launch_model(const LaunchShape& s, const BatchArgs& a, hipStream_t st) {
+    if (!s.implicit) {
+        if constexpr (Model::MAXB > kMaxTheta) return launch_place_big<Model>(s, a, st);
+        else return launch_place<Model>(s, a, st);
+    }
+    if constexpr (model_has_implicit<Model>()) return launch_place_implicit<Model>(s, a, st);
+    else return hipErrorInvalidValue;  // (muse_engine.cpp refuses the call before it gets here)
+}
+template <class Model>
+hipError_t loop_model(const LaunchShape& s, const LoopCall& c) {
+    if constexpr (Model::MAXB > kMaxTheta) return hipErrorNotSupported;
+    else return loop_place<Model>(s, c);
+}
+
+// Which models' kernels live in which translation unit (kernels_part.hip, -DMUSE_PART=n), one MUSE_MODEL per model: the models of
+// muse_kernels.hip's for_family, which declares them `extern`.
+#define MUSE_MODEL(X, M)                                                                       \
+    X template hipError_t launch_model<M>(const LaunchShape&, const BatchArgs&, hipStream_t);  \
+    X template hipError_t loop_model<M>(const LaunchShape&, const LoopCall&);
+#if defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_RESPONSE)   // a response behind the stencil operator: the link model's tiers
+#define MUSE_PART_0(X) MUSE_MODEL(X, UserResponseModel<2>)
+#define MUSE_PART_1(X) MUSE_MODEL(X, UserResponseModel<4>)
+#define MUSE_PART_2(X) MUSE_MODEL(X, UserResponseModel<kMaxTheta>)
+#define MUSE_PART_3(X) MUSE_MODEL(X, UserResponseModel<kBigTheta>)
+#elif defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_PAIR)     // two parameters per block: 1, 2, up to 4 blocks; no big tier
+#define MUSE_PART_0(X) MUSE_MODEL(X, UserModel<2>)
+#define MUSE_PART_1(X) MUSE_MODEL(X, UserModel<4>)
+#define MUSE_PART_2(X) MUSE_MODEL(X, UserModel<kMaxTheta>)
 #elif defined(MUSE_USER_MODEL_HEADER)
-#ifdef MUSE_MODEL_SECOND
-#define MUSE_INSTANTIATE_USER(X, M)                                                                \
-    X template hipError_t launch_place<M>(const LaunchShape&, const BatchArgs&, hipStream_t);       \
-    X template hipError_t launch_place_implicit<M>(const LaunchShape&, const BatchArgs&, hipStream_t); \
-    X template hipError_t loop_place<M>(const LaunchShape&, const LoopCall&);
-#define MUSE_INSTANTIATE_USER_BIG(X, M) MUSE_INSTANTIATE_BIG(X, M)
+#define MUSE_PART_0(X) MUSE_MODEL(X, UserModel<1>)
+#define MUSE_PART_1(X) MUSE_MODEL(X, UserModel<kMaxTheta>)
+#define MUSE_PART_2(X) MUSE_MODEL(X, UserModel<kBigTheta>)
 #else
-#define MUSE_INSTANTIATE_USER(X, M)                                                                 \
-    X template hipError_t launch_place<M>(const LaunchShape&, const BatchArgs&, hipStream_t);       \
-    X template hipError_t loop_place<M>(const LaunchShape&, const LoopCall&);
-#define MUSE_INSTANTIATE_USER_BIG(X, M) X template hipError_t launch_place_big<M>(const LaunchShape&, const BatchArgs&, hipStream_t);
+#define MUSE_PART_0(X) MUSE_MODEL(X, FunnelModel<1>)
+#define MUSE_PART_1(X) MUSE_MODEL(X, FunnelModel<2>)
+#define MUSE_PART_2(X) MUSE_MODEL(X, FunnelModel<4>)
+#define MUSE_PART_3(X) MUSE_MODEL(X, FunnelModel<kMaxTheta>)
+#define MUSE_PART_4(X) MUSE_MODEL(X, NoiseModel)
+#define MUSE_PART_5(X) MUSE_MODEL(X, SmoothModel<2>) MUSE_MODEL(X, SmoothModel<4>) MUSE_MODEL(X, SmoothTapsModel<2>) \
+                       MUSE_MODEL(X, SmoothTapsModel<4>) MUSE_MODEL(X, SmoothNoiseModel<2>) MUSE_MODEL(X, SmoothNoiseModel<4>)
+#define MUSE_PART_6(X) MUSE_MODEL(X, SmoothModel<kMaxTheta>) MUSE_MODEL(X, SmoothModel<kBigTheta>) MUSE_MODEL(X, SmoothTapsModel<kMaxTheta>) \
+                       MUSE_MODEL(X, SmoothTapsModel<kBigTheta>) MUSE_MODEL(X, SmoothNoiseModel<kMaxTheta>) MUSE_MODEL(X, SmoothNoiseModel<kBigTheta>)
+#define MUSE_PART_7(X) MUSE_MODEL(X, FunnelModel<kBigTheta>) MUSE_MODEL(X, SmoothLinkModel<2>) MUSE_MODEL(X, SmoothLinkModel<4>) \
+                       MUSE_MODEL(X, SmoothLinkModel<kMaxTheta>) MUSE_MODEL(X, SmoothLinkModel<kBigTheta>)
 #endif
-#ifdef MUSE_MODEL_PAIR   // two parameters per block: tiers of 2, 4 and 8 components (1, 2, up to 4 blocks); no big tier; the implicit
-                         // differentiation's kernels for a header that states its second derivatives (MUSE_MODEL_PAIR_SECOND) only
-#ifdef MUSE_MODEL_PAIR_SECOND
-#define MUSE_INSTANTIATE_PAIR(X, M)                                                                 \
-    X template hipError_t launch_place<M>(const LaunchShape&, const BatchArgs&, hipStream_t);       \
-    X template hipError_t launch_place_implicit<M>(const LaunchShape&, const BatchArgs&, hipStream_t); \
-    X template hipError_t loop_place<M>(const LaunchShape&, const LoopCall&);
-#else
-#define MUSE_INSTANTIATE_PAIR(X, M)                                                                 \
-    X template hipError_t launch_place<M>(const LaunchShape&, const BatchArgs&, hipStream_t);       \
-    X template hipError_t loop_place<M>(const LaunchShape&, const LoopCall&);
-#endif
-#define MUSE_PART_0(X) MUSE_INSTANTIATE_PAIR(X, UserModel<2>)
-#define MUSE_PART_1(X) MUSE_INSTANTIATE_PAIR(X, UserModel<4>)
-#define MUSE_PART_2(X) MUSE_INSTANTIATE_PAIR(X, UserModel<kMaxTheta>)
-#else
-#define MUSE_PART_0(X) MUSE_INSTANTIATE_USER(X, UserModel<1>)
-#define MUSE_PART_1(X) MUSE_INSTANTIATE_USER(X, UserModel<kMaxTheta>)
-#define MUSE_PART_2(X) MUSE_INSTANTIATE_USER_BIG(X, UserModel<kBigTheta>)
-#endif
+#ifdef MUSE_USER_MODEL_HEADER   // (a user's library holds the tiers of ONE family: its other units are empty)
+#ifndef MUSE_PART_3
 #define MUSE_PART_3(X)
+#endif
 #define MUSE_PART_4(X)
 #define MUSE_PART_5(X)
 #define MUSE_PART_6(X)
 #define MUSE_PART_7(X)
-#else
-#define MUSE_PART_0(X) MUSE_INSTANTIATE_ELEMENTWISE(X, FunnelModel<1>)
-#define MUSE_PART_1(X) MUSE_INSTANTIATE_ELEMENTWISE(X, FunnelModel<2>)
-#define MUSE_PART_2(X) MUSE_INSTANTIATE_ELEMENTWISE(X, FunnelModel<4>)
-#define MUSE_PART_3(X) MUSE_INSTANTIATE_ELEMENTWISE(X, FunnelModel<kMaxTheta>)
-#define MUSE_PART_4(X) MUSE_INSTANTIATE_ELEMENTWISE(X, NoiseModel)
-#define MUSE_PART_5(X) MUSE_INSTANTIATE_STENCIL(X, SmoothModel<2>) MUSE_INSTANTIATE_STENCIL(X, SmoothModel<4>) \
-                       MUSE_INSTANTIATE_STENCIL(X, SmoothTapsModel<2>) MUSE_INSTANTIATE_STENCIL(X, SmoothTapsModel<4>) \
-                       MUSE_INSTANTIATE_STENCIL(X, SmoothNoiseModel<2>) MUSE_INSTANTIATE_STENCIL(X, SmoothNoiseModel<4>)
-#define MUSE_PART_6(X) MUSE_INSTANTIATE_STENCIL(X, SmoothModel<kMaxTheta>) MUSE_INSTANTIATE_BIG(X, SmoothModel<kBigTheta>) \
-                       MUSE_INSTANTIATE_STENCIL(X, SmoothTapsModel<kMaxTheta>) MUSE_INSTANTIATE_BIG(X, SmoothTapsModel<kBigTheta>) \
-                       MUSE_INSTANTIATE_STENCIL(X, SmoothNoiseModel<kMaxTheta>) MUSE_INSTANTIATE_BIG(X, SmoothNoiseModel<kBigTheta>)
-#define MUSE_PART_7(X) MUSE_INSTANTIATE_BIG(X, FunnelModel<kBigTheta>) \
-                       MUSE_INSTANTIATE_STENCIL_MAP(X, SmoothLinkModel<2>) MUSE_INSTANTIATE_STENCIL_MAP(X, SmoothLinkModel<4>) \
-                       MUSE_INSTANTIATE_STENCIL_MAP(X, SmoothLinkModel<kMaxTheta>) MUSE_INSTANTIATE_BIG_MAP(X, SmoothLinkModel<kBigTheta>)
 #endif
 constexpr int kKernelParts = 8;
 }  // namespace muse

@@ -259,27 +259,32 @@ static bool tier_big(const muse_ctx* c, int pl, int nmaps) {
     if (kPairModel) return false;   // (one tier: models.hpp, UserModel of the two-parameter family)
     return !c->sw.no_big_tier && c->ntheta > 1 && !stencil_ctx(c) && nmaps <= 1 && (pl == P_S256 || pl == P_S512 || pl == P_C256);
 }
+// A context's launch in placement `pl`, as far as the context alone decides it; the caller sets what its launch adds (args.hpp, LaunchShape).
+static LaunchShape shape_of(const muse_ctx* c, int pl) {
+    LaunchShape s;
+    s.model = c->model; s.ntheta = c->ntheta; s.place = pl;
+    s.taps = c->stencil_taps; s.noise = c->noise_on; s.link = c->link_on;
+    return s;
+}
 // The fence of the resident MAP kernels, as loop_usable fences the loop kernel: a map kernel beyond the product's bound on scratch
 // (tools/regs.py, LIBRARY_SCRATCH_LIMIT; the regime in which spill code was seen to lose uniform values held across the solve) is
 // not launched.  Bit pl of the result: resident placement pl is such a kernel for this (model, ntheta).  Read from the code object
 // once per device and tier (hipFuncGetAttributes: no launch); libraries of user-supplied elementwise models only -- the kernels of
 // libmuse_hip.so are checked when it is built (tests/test_kernel_resources.py).
-static unsigned map_unfit_mask(int device, int model, int ntheta) {
+static unsigned map_unfit_mask(const muse_ctx* c) {
 #if defined(MUSE_USER_MODEL_HEADER) && !defined(MUSE_MODEL_RESPONSE)
     constexpr int kMapScratchLimit = 256;
     // (filled without a lock while muse_ctx_create may run on several threads: every thread that finds an entry empty computes the
     //  same word from the same code object and stores it whole -- a repeated query, never a wrong answer)
     static unsigned seen[64][kMaxTheta + 1];   // 0: not yet; bit 31: known
+    const int device = c->device, ntheta = c->ntheta;
     if (device < 0 || device >= 64 || ntheta < 1 || ntheta > kMaxTheta) return 0;
     if (!seen[device][ntheta]) {
         unsigned mask = 0x80000000u;
         static const BatchArgs none = BatchArgs();
         for (int pl : {P_R256x1, P_R512x4, P_R512x10, P_CR2, P_CR4, P_CR8}) {
             int bytes = 0;
-            LaunchShape shape;
-            shape.model = model; shape.ntheta = ntheta; shape.place = pl; shape.grid = 1; shape.implicit = false; shape.jacobi = false;
-            shape.big = false; shape.lds_s = false; shape.taps = false; shape.noise = false; shape.link = false; shape.lds = 0;
-            shape.done_event = nullptr;
+            LaunchShape shape = shape_of(c, pl);
             shape.scratch_query = &bytes;
             if (launch_solver(shape, none, nullptr) != hipSuccess) {
                 (void)hipGetLastError();
@@ -291,7 +296,7 @@ static unsigned map_unfit_mask(int device, int model, int ntheta) {
     }
     return seen[device][ntheta] & 0x7fffffffu;
 #else
-    (void)device; (void)model; (void)ntheta;
+    (void)c;
     return 0;
 #endif
 }
@@ -498,14 +503,11 @@ static int launch_batch(muse_ctx* c, BatchArgs& a, hipEvent_t done = nullptr, bo
     const bool timed = c->timing || c->prof_on;
     if (timed) HIPCHK(hipEventRecord(e0, c->lane->stream));
     {
-        LaunchShape shape;
-        shape.model = c->model; shape.ntheta = c->ntheta; shape.place = pl; shape.grid = grid; shape.implicit = implicit; shape.lds = lds;
+        LaunchShape shape = shape_of(c, pl);
+        shape.grid = grid; shape.implicit = implicit; shape.lds = lds;
         shape.jacobi = implicit && jacobi;
         shape.big = tier_big(c, pl, a.nmaps);
         shape.lds_s = !implicit && pl == P_C256 && stencil_lds_s(c, a.csize);
-        shape.taps = c->stencil_taps;
-        shape.noise = c->noise_on;
-        shape.link = c->link_on;
         shape.done_event = done;
         const hipError_t e = launch_solver(shape, a, c->lane->stream);
         if (e == hipErrorNotSupported && shape.jacobi)   // (kernels.hpp, launch_one: nothing was launched)
@@ -736,7 +738,7 @@ int muse_ctx_create(int model, int64_t N, int ntheta, int device, muse_ctx** out
             c->bnd[k] = ((int64_t)kk * N + nb - 1) / nb;
         }
     }
-    c->map_unfit = map_unfit_mask(device, model, ntheta);
+    c->map_unfit = map_unfit_mask(c);
     HIPCHK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
     {
         const int rc = use_lane(c, 0);
@@ -1760,10 +1762,7 @@ static bool loop_usable(muse_ctx* c, int S, int64_t nlocal, LaunchShape* shape_o
     const int nt = c->ntheta;
     const int64_t nprob_total = (int64_t)S + 1;
     const int pl = choose_place(c);
-    LaunchShape shape;
-    shape.model = c->model; shape.ntheta = nt; shape.place = pl; shape.grid = 0; shape.implicit = false; shape.jacobi = false; shape.lds_s = false; shape.taps = false; shape.noise = false; shape.link = false;
-    shape.big = false;  // (the loop kernel runs the resident placements)
-    shape.done_event = nullptr;
+    LaunchShape shape = shape_of(c, pl);   // (not the big tier: the loop kernel runs the resident placements)
     const bool xg_lds = pl == P_R512x10;
     shape.lds = place_lds(c, pl) + loop_extra_lds(xg_lds, nprob_total, nt);
     const bool host_only = c->sw.no_loop_kernel;  // tuning aid

@@ -283,104 +283,41 @@ namespace muse {
 MUSE_PART_0(extern) MUSE_PART_1(extern) MUSE_PART_2(extern) MUSE_PART_3(extern) MUSE_PART_4(extern) MUSE_PART_5(extern) MUSE_PART_6(extern) MUSE_PART_7(extern)
 #endif
 
+// The models this library holds: THE list (kernels.hpp instantiates it, one MUSE_MODEL per model, and a new variant adds itself in
+// both).  A family's tiers (tiers.hpp) go to f; a model, or a variant of it, that the library does not hold is refused.
+template <class F>
+static hipError_t for_family(int model, bool taps, bool noise, bool link, F&& f) {
+#if defined(MUSE_USER_MODEL_HEADER)   // a library built from a user's model header holds that model only (user_model.hpp)
+    if (model != MUSE_MODEL_USER) return hipErrorInvalidValue;
+#if defined(MUSE_MODEL_RESPONSE)      // a response behind the stencil operator: every launch carries a link, weights and noise as set
+    return link ? f(StencilTiers<UserResponseModel>{}) : hipErrorInvalidValue;
+#elif defined(MUSE_MODEL_PAIR)        // the two-parameter family
+    return taps || noise || link ? hipErrorInvalidValue : f(PairTiers<UserModel>{});
+#else
+    return taps || noise || link ? hipErrorInvalidValue : f(ElementwiseTiers<UserModel>{});
+#endif
+#else
+    if (model == MUSE_MODEL_NOISE) return f(Tiers<NoiseModel>{});
+    if (model == MUSE_MODEL_FUNNEL) return f(FunnelTiers<FunnelModel>{});
+    if (model != MUSE_MODEL_SMOOTH) return hipErrorInvalidValue;
+    if (link) return f(StencilTiers<SmoothLinkModel>{});
+    if (noise) return f(StencilTiers<SmoothNoiseModel>{});
+    if (taps) return f(StencilTiers<SmoothTapsModel>{});
+    return f(StencilTiers<SmoothModel>{});
+#endif
+}
+// ... and a launch's own: call(ModelTag<M>) for the tier the rule gives it
+template <TierPolicy P, class F>
+static hipError_t for_model(int model, bool taps, bool noise, bool link, int ntheta, bool big, F&& call) {
+    return for_family(model, taps, noise, link, [&](auto tiers) { return pick_tier<P>(tiers, ntheta, big, hipErrorInvalidValue, call); });
+}
+
 hipError_t launch_solver(const LaunchShape& s, const BatchArgs& a, hipStream_t st) {
 #ifdef MUSE_INSPECT  // development aid (tools/regs.py --check): instantiate ONE kernel, for a quick look at its assembly
     return launch_one<MUSE_INSPECT>(s, a, st);
-#elif defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_PAIR)   // ... of the two-parameter family: 2 ... kMaxTheta components, no big tier,
-    if (s.model != MUSE_MODEL_USER || s.big) return hipErrorInvalidValue;
-    if (s.implicit) {   // implicit differentiation: a header that states its second derivatives (MUSE_MODEL_PAIR_SECOND)
-#ifdef MUSE_MODEL_PAIR_SECOND
-        return s.ntheta == 2 ? launch_place_implicit<UserModel<2>>(s, a, st) : s.ntheta <= 4 ? launch_place_implicit<UserModel<4>>(s, a, st)
-                                                                                             : launch_place_implicit<UserModel<kMaxTheta>>(s, a, st);
 #else
-        return hipErrorInvalidValue;  // (muse_engine.cpp refuses the call before it gets here)
-#endif
-    }
-    return s.ntheta == 2 ? launch_place<UserModel<2>>(s, a, st) : s.ntheta <= 4 ? launch_place<UserModel<4>>(s, a, st)
-                                                                                : launch_place<UserModel<kMaxTheta>>(s, a, st);
-#elif defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_RESPONSE)   // ... a response behind the stencil operator: the link model's kernels
-    if (s.model != MUSE_MODEL_USER || !s.link) return hipErrorInvalidValue;
-    if (s.implicit) {   // implicit differentiation: a header that states phi'' (MUSE_MODEL_RESPONSE_SECOND)
-#ifdef MUSE_MODEL_RESPONSE_SECOND
-        if (s.jacobi) return hipErrorInvalidValue;  // (muse_engine.cpp refuses the call before it gets here)
-        if (s.big) return launch_place_implicit<UserResponseModel<kBigTheta>>(s, a, st);
-        return s.ntheta <= 2 ? launch_place_implicit<UserResponseModel<2>>(s, a, st) : s.ntheta <= 4 ? launch_place_implicit<UserResponseModel<4>>(s, a, st)
-                                                                                                  : launch_place_implicit<UserResponseModel<kMaxTheta>>(s, a, st);
-#else
-        return hipErrorInvalidValue;  // (muse_engine.cpp refuses the call before it gets here)
-#endif
-    }
-    if (s.big) return launch_place_big<UserResponseModel<kBigTheta>>(s, a, st);
-    return s.ntheta <= 2 ? launch_place<UserResponseModel<2>>(s, a, st) : s.ntheta <= 4 ? launch_place<UserResponseModel<4>>(s, a, st)
-                                                                                      : launch_place<UserResponseModel<kMaxTheta>>(s, a, st);
-#elif defined(MUSE_USER_MODEL_HEADER)  // a library built from a user's model header holds that model only (user_model.hpp)
-    if (s.model != MUSE_MODEL_USER) return hipErrorInvalidValue;
-    if (s.big && !s.implicit) return launch_place_big<UserModel<kBigTheta>>(s, a, st);
-    if (s.implicit) {
-#ifdef MUSE_MODEL_SECOND
-        if (s.big) return launch_place_implicit<UserModel<kBigTheta>>(s, a, st);
-        return s.ntheta == 1 ? launch_place_implicit<UserModel<1>>(s, a, st) : launch_place_implicit<UserModel<kMaxTheta>>(s, a, st);
-#else
-        return hipErrorInvalidValue;  // (muse_engine.cpp refuses the call before it gets here)
-#endif
-    }
-    return s.ntheta == 1 ? launch_place<UserModel<1>>(s, a, st) : launch_place<UserModel<kMaxTheta>>(s, a, st);
-#else
-    const int nt = s.ntheta;
-    if (s.big) {  // the big tier (args.hpp, BigTheta; muse_engine.cpp, tier_big): streaming placements only
-        if (s.model == MUSE_MODEL_FUNNEL)
-            return s.implicit ? launch_place_implicit<FunnelModel<kBigTheta>>(s, a, st) : launch_place_big<FunnelModel<kBigTheta>>(s, a, st);
-        if (s.model == MUSE_MODEL_SMOOTH && s.link)   // (map kernels only: muse_engine.cpp refuses the implicit pass of a context with a link)
-            return s.implicit ? hipErrorInvalidValue : launch_place_big<SmoothLinkModel<kBigTheta>>(s, a, st);
-        if (s.model == MUSE_MODEL_SMOOTH && s.noise)
-            return s.implicit ? launch_place_implicit<SmoothNoiseModel<kBigTheta>>(s, a, st) : launch_place_big<SmoothNoiseModel<kBigTheta>>(s, a, st);
-        if (s.model == MUSE_MODEL_SMOOTH && s.taps)
-            return s.implicit ? launch_place_implicit<SmoothTapsModel<kBigTheta>>(s, a, st) : launch_place_big<SmoothTapsModel<kBigTheta>>(s, a, st);
-        if (s.model == MUSE_MODEL_SMOOTH)
-            return s.implicit ? launch_place_implicit<SmoothModel<kBigTheta>>(s, a, st) : launch_place_big<SmoothModel<kBigTheta>>(s, a, st);
-        return hipErrorInvalidValue;
-    }
-    if (s.implicit) {
-        if (s.model == MUSE_MODEL_NOISE) return launch_place_implicit<NoiseModel>(s, a, st);
-        if (s.model == MUSE_MODEL_FUNNEL)
-            return nt == 1   ? launch_place_implicit<FunnelModel<1>>(s, a, st)
-                   : nt == 2 ? launch_place_implicit<FunnelModel<2>>(s, a, st)
-                   : nt <= 4 ? launch_place_implicit<FunnelModel<4>>(s, a, st)
-                             : launch_place_implicit<FunnelModel<kMaxTheta>>(s, a, st);
-        if (s.link) return hipErrorInvalidValue;   // (muse_engine.cpp refuses the call before it gets here)
-        if (s.noise)
-            return nt <= 2   ? launch_place_implicit<SmoothNoiseModel<2>>(s, a, st)
-                   : nt <= 4 ? launch_place_implicit<SmoothNoiseModel<4>>(s, a, st)
-                             : launch_place_implicit<SmoothNoiseModel<kMaxTheta>>(s, a, st);
-        if (s.taps)
-            return nt <= 2   ? launch_place_implicit<SmoothTapsModel<2>>(s, a, st)
-                   : nt <= 4 ? launch_place_implicit<SmoothTapsModel<4>>(s, a, st)
-                             : launch_place_implicit<SmoothTapsModel<kMaxTheta>>(s, a, st);
-        return nt <= 2   ? launch_place_implicit<SmoothModel<2>>(s, a, st)
-               : nt <= 4 ? launch_place_implicit<SmoothModel<4>>(s, a, st)
-                         : launch_place_implicit<SmoothModel<kMaxTheta>>(s, a, st);
-    }
-    if (s.model == MUSE_MODEL_NOISE) return launch_place<NoiseModel>(s, a, st);
-    if (s.model == MUSE_MODEL_FUNNEL)
-        return nt == 1   ? launch_place<FunnelModel<1>>(s, a, st)
-               : nt == 2 ? launch_place<FunnelModel<2>>(s, a, st)
-               : nt <= 4 ? launch_place<FunnelModel<4>>(s, a, st)
-                         : launch_place<FunnelModel<kMaxTheta>>(s, a, st);
-    if (s.link)
-        return nt <= 2   ? launch_place<SmoothLinkModel<2>>(s, a, st)
-               : nt <= 4 ? launch_place<SmoothLinkModel<4>>(s, a, st)
-                         : launch_place<SmoothLinkModel<kMaxTheta>>(s, a, st);
-    if (s.noise)
-        return nt <= 2   ? launch_place<SmoothNoiseModel<2>>(s, a, st)
-               : nt <= 4 ? launch_place<SmoothNoiseModel<4>>(s, a, st)
-                         : launch_place<SmoothNoiseModel<kMaxTheta>>(s, a, st);
-    if (s.taps)
-        return nt <= 2   ? launch_place<SmoothTapsModel<2>>(s, a, st)
-               : nt <= 4 ? launch_place<SmoothTapsModel<4>>(s, a, st)
-                         : launch_place<SmoothTapsModel<kMaxTheta>>(s, a, st);
-    return nt <= 2   ? launch_place<SmoothModel<2>>(s, a, st)
-           : nt <= 4 ? launch_place<SmoothModel<4>>(s, a, st)
-                     : launch_place<SmoothModel<kMaxTheta>>(s, a, st);
+    return for_model<TIER_FIRST_FIT>(s.model, s.taps, s.noise, s.link, s.ntheta, s.big,
+                                     [&](auto m) { return launch_model<typename decltype(m)::type>(s, a, st); });
 #endif
 }
 
@@ -389,24 +326,9 @@ static hipError_t loop_dispatch(const LaunchShape& s, const LoopCall& c) {
     return loop_one<MUSE_INSPECT_LOOP>(s, c);
 #elif defined(MUSE_INSPECT)
     return hipErrorNotSupported;
-#elif defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_RESPONSE)
-    (void)c;
-    return s.model != MUSE_MODEL_USER ? hipErrorInvalidValue : hipErrorNotSupported;  // the stencil model streams
-#elif defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_PAIR)
-    if (s.model != MUSE_MODEL_USER) return hipErrorInvalidValue;
-    return s.ntheta == 2 ? loop_place<UserModel<2>>(s, c) : s.ntheta <= 4 ? loop_place<UserModel<4>>(s, c) : loop_place<UserModel<kMaxTheta>>(s, c);
-#elif defined(MUSE_USER_MODEL_HEADER)
-    if (s.model != MUSE_MODEL_USER) return hipErrorInvalidValue;
-    return s.ntheta == 1 ? loop_place<UserModel<1>>(s, c) : loop_place<UserModel<kMaxTheta>>(s, c);
 #else
-    const int nt = s.ntheta;
-    if (s.model == MUSE_MODEL_NOISE) return loop_place<NoiseModel>(s, c);
-    if (s.model == MUSE_MODEL_FUNNEL)
-        return nt == 1   ? loop_place<FunnelModel<1>>(s, c)
-               : nt == 2 ? loop_place<FunnelModel<2>>(s, c)
-               : nt <= 4 ? loop_place<FunnelModel<4>>(s, c)
-                         : loop_place<FunnelModel<kMaxTheta>>(s, c);
-    return hipErrorNotSupported;  // the stencil model streams
+    return for_model<TIER_FIRST_FIT>(s.model, s.taps, s.noise, s.link, s.ntheta, s.big,
+                                     [&](auto m) { return loop_model<typename decltype(m)::type>(s, c); });
 #endif
 }
 bool loop_supported(const LaunchShape& s) {
@@ -532,37 +454,10 @@ hipError_t launch_sample(int model, bool taps, bool noisy, bool link, const Batc
 }
 
 hipError_t launch_loglike(int model, bool taps, bool noise, bool link, const BatchArgs& a, const double* x, const double* z, double* g, double* out, hipStream_t st) {
-#if defined(MUSE_USER_MODEL_HEADER) && defined(MUSE_MODEL_RESPONSE)
-    (void)taps; (void)noise;
-    if (model != MUSE_MODEL_USER || !link) return hipErrorInvalidValue;
-    if (a.ntheta > kMaxTheta) hipLaunchKernelGGL(loglike_kernel<UserResponseModel<kBigTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
-    else hipLaunchKernelGGL(loglike_kernel<UserResponseModel<kMaxTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
-    return hipGetLastError();
-#else
-#ifdef MUSE_USER_MODEL_HEADER
-    if (model != MUSE_MODEL_USER || taps || noise || link) return hipErrorInvalidValue;
-#ifdef MUSE_MODEL_PAIR
-    if (a.ntheta > kMaxTheta) return hipErrorInvalidValue;
-#else
-    if (a.ntheta > kMaxTheta) hipLaunchKernelGGL(loglike_kernel<UserModel<kBigTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
-    else
-#endif
-    hipLaunchKernelGGL(loglike_kernel<UserModel<kMaxTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
-    return hipGetLastError();
-#endif
-    if (model == MUSE_MODEL_NOISE) hipLaunchKernelGGL(loglike_kernel<NoiseModel>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
-    else if (model == MUSE_MODEL_FUNNEL && a.ntheta > kMaxTheta) hipLaunchKernelGGL(loglike_kernel<FunnelModel<kBigTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
-    else if (model == MUSE_MODEL_FUNNEL) hipLaunchKernelGGL(loglike_kernel<FunnelModel<kMaxTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
-    else if (link && a.ntheta > kMaxTheta) hipLaunchKernelGGL(loglike_kernel<SmoothLinkModel<kBigTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
-    else if (link) hipLaunchKernelGGL(loglike_kernel<SmoothLinkModel<kMaxTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
-    else if (noise && a.ntheta > kMaxTheta) hipLaunchKernelGGL(loglike_kernel<SmoothNoiseModel<kBigTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
-    else if (noise) hipLaunchKernelGGL(loglike_kernel<SmoothNoiseModel<kMaxTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
-    else if (taps && a.ntheta > kMaxTheta) hipLaunchKernelGGL(loglike_kernel<SmoothTapsModel<kBigTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
-    else if (taps) hipLaunchKernelGGL(loglike_kernel<SmoothTapsModel<kMaxTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
-    else if (a.ntheta > kMaxTheta) hipLaunchKernelGGL(loglike_kernel<SmoothModel<kBigTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
-    else hipLaunchKernelGGL(loglike_kernel<SmoothModel<kMaxTheta>>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
-    return hipGetLastError();
-#endif
+    return for_model<TIER_WIDEST>(model, taps, noise, link, a.ntheta, a.ntheta > kMaxTheta, [&](auto m) {
+        hipLaunchKernelGGL(loglike_kernel<typename decltype(m)::type>, dim3(1), dim3(1024), 0, st, a, x, z, g, out);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace muse
